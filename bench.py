@@ -6,7 +6,12 @@ neighbour-list rebuild every 10th step) over the synthetic DamBreak3D box (SURVE
 all inputs resident in HBM.  Metric = 1e-6 * sum over timed steps of internal particles / wall
 seconds = GPUSPH's MIPPS (src/timing.h:136-164).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--particles P]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--particles P] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes work of its own: the roofline
+object (HIP events around the dominant forces kernel during the timed steps, PMC traffic from the committed profiles) and the
+CPU baseline (skipped with --no-cpu-baseline).  --dump-outputs DIR writes the state the last timed step left (a fixed sample
+of the particles, in particle-id order) as DIR/<name>.npy.
 
 For N > 1 the driver launches one rank per GPU (torch.distributed.run); the domain is slab-split
 (strong scaling: the total particle count is fixed).
@@ -111,6 +116,38 @@ def pmc_traffic(n_total, kernel):
     return None
 
 
+DUMP_SAMPLE = 1 << 19               # particles written by --dump-outputs: 80 B each in float32/float64, 40 MB in all
+DUMP_SEED = 20240607
+
+
+def dump_outputs(eng, out_dir, rank=0, world=1):
+    """what the timed path hands its caller after the last timed step: positions (local to the cell), velocities, forces,
+    cell hashes and particle infos of a fixed, seeded sample of the particles, ordered by particle id, and the time step.
+    Same arguments, same sample: two builds compare array for array"""
+    import torch
+    n = int(eng.n_int)
+    info = eng.info[:n]
+    ids = (info[:, 2].to(torch.int64) & 0xFFFF) | ((info[:, 3].to(torch.int64) & 0xFFFF) << 16)
+    sorted_ids, order = torch.sort(ids)
+    if n > DUMP_SAMPLE:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+        order = order[torch.from_numpy(pick).to(order.device)]
+        sorted_ids = sorted_ids[torch.from_numpy(pick).to(order.device)]
+    arrays = {
+        "id": sorted_ids.cpu().numpy().astype(np.float64),
+        "pos": eng.pos[:n][order].cpu().numpy().astype(np.float32),
+        "vel": eng.vel[:n][order].cpu().numpy().astype(np.float32),
+        "forces": eng.forces[:n][order].cpu().numpy().astype(np.float32),
+        "hash": eng.hash[:n][order].cpu().numpy().view(np.uint32).astype(np.float64),
+        "info": info[order].cpu().numpy().view(np.uint16).astype(np.float32),
+        "dt": np.array([eng.current_dt()], dtype=np.float64),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+
+
 def self_launch(n):
     """one rank per GPU under torch.distributed.run on this node (what the driver's command line does for N > 1), same arguments"""
     import socket
@@ -136,7 +173,9 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--particles", type=float, default=DEFAULT_PARTICLES)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the roofline object and the CPU baseline (work beyond the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the state after the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--no-obstacle", action="store_true")
     ap.add_argument("--no-tiles", action="store_true", help="A/B: use the generic gather forces kernel")
     ap.add_argument("--two-fluids", action="store_true", help="A/B: a lighter second fluid on top (multi-fluid code path)")
@@ -237,12 +276,13 @@ def main():
         eng.halo_bytes = 0
         eng.exchange_events = []
     info = eng.neibs_info()                 # also checks for neighbour-list overflow
-    # HIP events on the launch stream around the dominant kernel of every forces pass, recorded by the library
+    # --full: HIP events on the launch stream around the dominant kernel of every forces pass, recorded by the library
     import ctypes as C
     from gpusph_amd import capi
     ctx = eng.ctx if hasattr(eng, "ctx") else eng.k.ctx
     lib = eng.lib if hasattr(eng, "lib") else eng.k.lib
-    capi.check(lib.sphx_forces_timing(ctx.handle, 1))
+    if args.full:
+        capi.check(lib.sphx_forces_timing(ctx.handle, 1))
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -253,11 +293,15 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    tot_ms, launches = C.c_double(0.0), C.c_uint32(0)
-    capi.check(lib.sphx_forces_timing_read(ctx.handle, C.byref(tot_ms), C.byref(launches)))
-    capi.check(lib.sphx_forces_timing(ctx.handle, 0))
-    # one figure per forces PASS (a multi-GPU pass is an edge-stripe plus an inner-stripe launch)
-    forces_ms = [tot_ms.value / (2 * args.steps)] if launches.value else []
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, rank, world)
+    forces_ms = []
+    if args.full:
+        tot_ms, launches = C.c_double(0.0), C.c_uint32(0)
+        capi.check(lib.sphx_forces_timing_read(ctx.handle, C.byref(tot_ms), C.byref(launches)))
+        capi.check(lib.sphx_forces_timing(ctx.handle, 0))
+        # one figure per forces PASS (a multi-GPU pass is an edge-stripe plus an inner-stripe launch)
+        forces_ms = [tot_ms.value / (2 * args.steps)] if launches.value else []
     n_internal = eng.internal_particles() if hasattr(eng, "internal_particles") else eng.n
     n64 = C.c_uint64(0)      # the 32-bit counter of the reference's interface wraps at 33 M particles x 65 neighbours
     capi.check(lib.sphx_neibs_interactions64(ctx.handle, C.byref(n64), None))
@@ -284,13 +328,6 @@ def main():
         updates = n_sum * args.steps
         value = 1e-6 * updates / elapsed
         nbar = interactions / max(n_internal, 1)
-        # algorithmic bytes of one forces launch on this rank: (64 + 2*Nbar) B per particle
-        # (own pos+vel+info+hash 44, list 2(Nbar+2), forces write 16) -- BASELINE.md section 3
-        bytes_per_launch = n_internal * (64.0 + 2.0 * nbar)
-        avg_ms = float(np.mean(forces_ms)) if forces_ms else float("nan")
-        achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if forces_ms else float("nan")
-        kernel = "forces_kernel" if args.no_tiles else "forces_tile_kernel"
-        traffic = None if (args.no_tiles or world > 1) else pmc_traffic(n_total, kernel)
         out = {
             "metric": "M particle-updates/sec, DamBreak3D", "value": round(value, 2),
             "unit": "M particle-updates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -301,19 +338,27 @@ def main():
                                    % (n_total, dp, "viscosity<%s>" % args.viscosity if args.viscosity else "artificial viscosity"),
                        "particles": n_total, "parallelism": "slab%d" % world if world > 1 else "single", "linearization": lin,
                        "mean_neibs": round(nbar, 2), "env": sphx_env()},
-            "roofline": {"bound": "hbm", "kernel": kernel, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "launch_ms": round(avg_ms, 4), "bytes_per_launch": int(bytes_per_launch),
-                         # what actually binds the pair loop: fp32 vector issue.  ~60 flop per stored pair
-                         # against the packed-fp32 peak of the chip
-                         "valu": {"bound": "valu", "achieved": round(interactions * 60.0 / (avg_ms * 1e-3) / 1e12, 2),
-                                  "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                  "frac": round(interactions * 60.0 / (avg_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 4),
-                                  "flop_per_pair": 60}},
         }
+        if args.full:
+            # algorithmic bytes of one forces launch on this rank: (64 + 2*Nbar) B per particle
+            # (own pos+vel+info+hash 44, list 2(Nbar+2), forces write 16) -- BASELINE.md section 3
+            bytes_per_launch = n_internal * (64.0 + 2.0 * nbar)
+            avg_ms = float(np.mean(forces_ms)) if forces_ms else float("nan")
+            achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if forces_ms else float("nan")
+            kernel = "forces_kernel" if args.no_tiles else "forces_tile_kernel"
+            traffic = None if (args.no_tiles or world > 1) else pmc_traffic(n_total, kernel)
+            out["roofline"] = {"bound": "hbm", "kernel": kernel, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                               "launch_ms": round(avg_ms, 4), "bytes_per_launch": int(bytes_per_launch),
+                               # what actually binds the pair loop: fp32 vector issue.  ~60 flop per stored pair
+                               # against the packed-fp32 peak of the chip
+                               "valu": {"bound": "valu", "achieved": round(interactions * 60.0 / (avg_ms * 1e-3) / 1e12, 2),
+                                        "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                        "frac": round(interactions * 60.0 / (avg_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 4),
+                                        "flop_per_pair": 60}}
         if exch is not None:
             out["exchange"] = exch
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if dist is not None:

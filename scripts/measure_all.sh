@@ -7,13 +7,13 @@ OUT=gpurun_out/measure
 mkdir -p $OUT
 export TMPDIR=/tmp
 # headline: DamBreak3D 31.8 M particles (bench default, with the CPU baseline), 8 M, 1 M, 128 M
-python bench.py > $OUT/bench32M.json 2> $OUT/bench32M.err
-python bench.py --no-cpu-baseline --particles 8e6 > $OUT/bench8M.json 2> /dev/null
-python bench.py --no-cpu-baseline --particles 1e6 --steps 200 --warmup 21 > $OUT/bench1M.json 2> /dev/null
-python bench.py --no-cpu-baseline --particles 128e6 --steps 12 --warmup 11 > $OUT/bench128M.json 2> /dev/null
+python bench.py --full > $OUT/bench32M.json 2> $OUT/bench32M.err
+python bench.py --full --no-cpu-baseline --particles 8e6 > $OUT/bench8M.json 2> /dev/null
+python bench.py --full --no-cpu-baseline --particles 1e6 --steps 200 --warmup 21 > $OUT/bench1M.json 2> /dev/null
+python bench.py --full --no-cpu-baseline --particles 128e6 --steps 12 --warmup 11 > $OUT/bench128M.json 2> /dev/null
 # option sets on the same build
-python bench.py --no-cpu-baseline --particles 8e6 --viscosity SPSVISC > $OUT/bench8M_spsvisc.json 2> /dev/null
-python bench.py --no-cpu-baseline --particles 8e6 --two-fluids > $OUT/bench8M_two_fluids.json 2> /dev/null
+python bench.py --full --no-cpu-baseline --particles 8e6 --viscosity SPSVISC > $OUT/bench8M_spsvisc.json 2> /dev/null
+python bench.py --full --no-cpu-baseline --particles 8e6 --two-fluids > $OUT/bench8M_two_fluids.json 2> /dev/null
 python scripts/time_stillwater.py 4e6 DYNAMICVISC > $OUT/stillwater_4M_dynamicvisc.txt 2>&1      # configs[2], DYN walls
 python scripts/time_stillwater.py 4e6 SPSVISC > $OUT/stillwater_4M_spsvisc.txt 2>&1
 python scripts/time_wavetank.py > $OUT/wavetank_5M.txt 2>&1                                       # configs[4]'s option set

@@ -17,6 +17,6 @@ python scripts/make_traffic_json.py $(ls gpurun_out/${TAG}t_fetch/*/*counter_col
 cp $(ls gpurun_out/${TAG}t_stats/*/*kernel_stats.csv) $OUT/${TAG}_bench32M_kernel_stats.csv
 python scripts/sq_summary.py $OUT/${TAG}_sq_32M.csv gpurun_out/${TAG}s32_sq1 gpurun_out/${TAG}s32_sq2 gpurun_out/${TAG}s32_sq3 > /dev/null
 python scripts/sq_summary.py $OUT/${TAG}_sq_8M.csv gpurun_out/${TAG}s8_sq1 gpurun_out/${TAG}s8_sq2 gpurun_out/${TAG}s8_sq3 > /dev/null
-python bench.py --no-cpu-baseline > $OUT/${TAG}_bench32M.json 2> /dev/null
-python bench.py --no-cpu-baseline --particles 8e6 > $OUT/${TAG}_bench8M.json 2> /dev/null
+python bench.py --full --no-cpu-baseline > $OUT/${TAG}_bench32M.json 2> /dev/null
+python bench.py --full --no-cpu-baseline --particles 8e6 > $OUT/${TAG}_bench8M.json 2> /dev/null
 ls -la $OUT

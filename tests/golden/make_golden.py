@@ -3,6 +3,8 @@
 
   ref_kernels.npz, ref_datamodel.npz   outputs of the REFERENCE's own code (oracle/_ref, compiled here
                                        from /root/reference/src/cuda/sph_core.cu, src/particleinfo.h, ...)
+  ref_vtkwriter_layout.json            array order and element types of the reference's particle writer
+                                       (read off src/writers/VTKWriter.cc of the GPUSPH tree named by $REF)
   oracle_pipeline.npz                  outputs of the CPU oracle on a small DamBreak3D (regression data for
                                        the GPU path; the oracle itself is unpinned for these stages)
 
@@ -304,7 +306,31 @@ def refgamma():
                         q_vb=qvb, gauss_quadrature_O5=gq, grad_gamma=gg, gamma_fluid=gaf, gamma_vertex=gav)
 
 
+def vtkwriter_layout():
+    """ref_vtkwriter_layout.json: the array layout of the reference's own particle writer, read off its source.  The sequence of
+    `appender.append_data(..., "Name"...)` calls gives the order of the arrays in a GPUSPH file, the accessor function each call
+    passes and the return types of those functions give the element types"""
+    import json, re
+    assert os.environ.get("REF"), "set REF to the GPUSPH tree (the REF of oracle/Makefile)"
+    text = open(os.path.join(os.environ["REF"], "src", "writers", "VTKWriter.cc")).read()
+    body = text[text.index("VTKAppender appender(fid, info, gdata, node_offset, numParts);"):]
+    body = body[:body.index("</AppendedData>")] if "</AppendedData>" in body else body
+    names, accessor = [], {}
+    calls = [m.start() for m in re.finditer(r"appender\.append_(?:local_)?data\(", body)]
+    for a, b in zip(calls, calls[1:] + [len(body)]):
+        args = body[a:b].split(";")[0].split("[")[0]            # one call: up to its ';' (or to a lambda argument)
+        found = re.findall(r'"([^"]+)"', args)
+        names += found
+        fn = re.search(r",\s*(get_\w+|demote_w|id)\s*\)\s*$", args.strip())
+        if fn and found:
+            accessor[found[0]] = fn.group(1)
+    returns = {fn: t for t, fn in re.findall(r"^(float|uchar|ushort|uint)\s+(get_\w+|demote_w)\(", text, re.M)}
+    with open(os.path.join(HERE, "ref_vtkwriter_layout.json"), "w") as f:
+        json.dump({"source": "src/writers/VTKWriter.cc", "names": names, "accessor": accessor, "returns": returns}, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    kernels(); datamodel(); viscavg(); hostparams(); refmisc(); refgamma(); pipeline(); features(); features2()
+    kernels(); datamodel(); viscavg(); hostparams(); refmisc(); refgamma(); pipeline(); features(); features2(); vtkwriter_layout()
     for f in sorted(os.listdir(HERE)):
         print(f, os.path.getsize(os.path.join(HERE, f)))

@@ -1,22 +1,22 @@
-"""Case files for the two host programs built against the GPUSPH tree (gpusph_amd/host/framework_check,
-example_engines): the parameters of a Python problem mirror written as "key value..." lines (see
+"""Case files for the two host programs built against the GPUSPH tree (oracle/_ref/host/framework_check,
+example_engines; sources in gpusph_amd/host): the parameters of a Python problem mirror written as "key value..." lines (see
 gpusph_amd/host/problem_setup.h).  Test infrastructure."""
 import math
 import os
-import subprocess
 import numpy as np
 
 from gpusph_amd import defs as D
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_DIR = os.path.join(ROOT, "gpusph_amd", "host")
+HOST_DIR = os.path.join(ROOT, "oracle", "_ref", "host")
 
 
 def exe(name):
-    """path of a prebuilt host program; builds it when the GPUSPH tree is here and it is missing"""
+    """path of a host program that build() made under oracle/_ref/host (oracle/Makefile, where the GPUSPH tree is present)"""
     path = os.path.join(HOST_DIR, name)
-    if not os.path.exists(path) and os.path.isdir("/root/reference/src"):
-        subprocess.check_call(["make", "-s", "-C", HOST_DIR, name])
+    if not os.path.exists(path):
+        raise FileNotFoundError("oracle/_ref/host/%s is not built: build() makes it where the GPUSPH tree is present "
+                                "(oracle/Makefile, target host)" % name)
     return path
 
 

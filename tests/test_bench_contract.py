@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -28,7 +29,7 @@ def test_no_gpu_no_bench_line():
 
 @pytest.mark.gpu
 def test_bench_line_contract():
-    r = _run(["--particles", "3e5", "--steps", "12", "--warmup", "11", "--no-cpu-baseline"], 600)
+    r = _run(["--particles", "3e5", "--steps", "12", "--warmup", "11", "--full", "--no-cpu-baseline"], 600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.lstrip().startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -52,6 +53,35 @@ def test_bench_line_contract():
     assert 2 * rf["launch_ms"] < d["ms_per_step"]    # two forces passes fit into a step
     assert rf["traffic"] is None                     # PMC traffic is only quoted for the profiled workload and build
     assert "cpu_baseline" not in d                   # --no-cpu-baseline
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """a plain run (no --full) prints the headline line alone, and --dump-outputs writes the state of the last timed step: the
+    same arrays, bit for bit, from two runs with the same arguments"""
+    lines, dumps = [], []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        r = _run(["--particles", "3e5", "--steps", "7", "--warmup", "11", "--dump-outputs", str(out)], 600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        ls = [l for l in r.stdout.splitlines() if l.lstrip().startswith("{")]
+        assert len(ls) == 1, r.stdout
+        lines.append(json.loads(ls[0]))
+        dumps.append({f.stem: np.load(f) for f in sorted(out.glob("*.npy"))})
+    d = lines[0]
+    for key in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert key in d, key
+    assert d["steps"] == 7 and d["warmup"] == 11 and "roofline" not in d and "cpu_baseline" not in d
+    assert abs(d["value"] - d["config"]["particles"] / d["ms_per_step"] / 1e3) <= 2e-3 * d["value"]
+    a, b = dumps
+    assert set(a) == {"id", "pos", "vel", "forces", "hash", "info", "dt"} and set(b) == set(a)
+    n = d["config"]["particles"]
+    assert len(a["id"]) == min(n, 1 << 19) and np.all(np.diff(a["id"]) > 0)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert np.array_equal(a[name].view(np.uint8), b[name].view(np.uint8)), name
+    assert np.abs(a["forces"][:, :3]).max() > 0 and a["dt"][0] > 0
 
 
 def test_self_launch_builds_the_drivers_command_line(monkeypatch):

@@ -153,7 +153,7 @@ def test_cpp_adapters_run_the_grenier_step_like_the_python_driver(tmp_path):
     import os, subprocess
     import host_case as hc
     exe = hc.exe("example_engines")
-    assert os.path.exists(exe), "gpusph_amd/host/example_engines is not built (make -C gpusph_amd/host, needs the GPUSPH tree)"
+    assert os.path.exists(exe), "oracle/_ref/host/example_engines is not built (make -C oracle host, needs the GPUSPH tree)"
     prob = grenier_problem(0.04, jitter=0.05)
     prob.simparams.simflags &= ~D.ENABLE_REPACKING           # the Bubble selector list of problem_setup.h has no repacking flag
     eng = _engine(prob)

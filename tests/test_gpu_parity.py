@@ -625,11 +625,11 @@ def test_two_ranks_on_one_gpu_equal_single_domain(tmp_path, casename, kernels, m
 
 
 # ---------------------------------------------------------------------------------------------
-# The host side of the boundary: gpusph_amd/host/example_engines is built INSIDE the GPUSPH tree (hip_engines.h derives
+# The host side of the boundary: oracle/_ref/host/example_engines is built INSIDE the GPUSPH tree (hip_engines.h derives
 # from the reference's own abstract engines, cudasimframework.cu answers the problems' SETUP_FRAMEWORK, buffers are the
 # tree's BufferList with the HIPBuffer policy) and sends one worker's command stream through those interfaces, with the
 # reference's blocking dtreduce.  It must leave bit-identical particles to the Python driver (same C-ABI calls,
-# device-resident dt).  The binary is prebuilt in the build container (the GPU box has no GPUSPH tree).
+# device-resident dt).  build() makes the binary where the tree is present; it travels with oracle/_ref.
 def _cpp_case(name):
     from gpusph_amd.problem import StillWater, WaveTank
     if name == "dambreak":      # DamBreak3D.cu framework; obstacle with force feedback, Shepard filter, surface detection
@@ -654,7 +654,7 @@ def test_cpp_adapters_match_python_engine(tmp_path, name):
     import os, subprocess
     import host_case as hc
     exe = hc.exe("example_engines")
-    assert os.path.exists(exe), "gpusph_amd/host/example_engines is not built (make -C gpusph_amd/host, needs the GPUSPH tree)"
+    assert os.path.exists(exe), "oracle/_ref/host/example_engines is not built (make -C oracle host, needs the GPUSPH tree)"
     prob, framework, selectors, filters, steps = _cpp_case(name)
     eng = _engine(prob)
     for ft, fq in filters:

@@ -113,7 +113,7 @@ def test_cpp_adapters_run_the_papanastasiou_step_like_the_python_driver(tmp_path
     import os, subprocess
     import host_case as hc
     exe = hc.exe("example_engines")
-    assert os.path.exists(exe), "gpusph_amd/host/example_engines is not built (make -C gpusph_amd/host, needs the GPUSPH tree)"
+    assert os.path.exists(exe), "oracle/_ref/host/example_engines is not built (make -C oracle host, needs the GPUSPH tree)"
     prob = Poiseuille(12, rheology=D.PAPANASTASIOU, compvisc=compvisc, viscavg=viscavg)
     eng = _engine(prob)
     steps = 12

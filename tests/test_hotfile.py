@@ -1,4 +1,5 @@
 """GPUSPH HotFile v1 round trip and the struct layouts the reference's scripts/hotdiff.py expects."""
+import os
 import struct
 import numpy as np
 import pytest
@@ -87,17 +88,21 @@ def test_resume_with_a_moving_body_is_bit_identical(tmp_path):
         assert np.array_equal(np.asarray(out[k]).view(np.uint8), np.asarray(ref[k]).view(np.uint8)), k
 
 
-@pytest.mark.skipif(not __import__("os").path.exists("/root/reference/scripts/hotdiff.py"),
-                    reason="the reference tree is only present in the build container")
+HOTDIFF = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "hotdiff.pyc")
+
+
+@pytest.mark.skipif(not os.path.exists(HOTDIFF),
+                    reason="oracle/_ref/hotdiff.pyc not built (build() makes it where the reference tree is present)")
 def test_reference_hotdiff_reads_our_files(tmp_path):
-    """the reference's own comparison tool walks two of our HotFiles end to end and finds no difference"""
+    """the reference's own comparison tool (scripts/hotdiff.py, byte-compiled into oracle/_ref by build()) walks two of our
+    HotFiles end to end and finds no difference"""
     import subprocess, sys
     prob = DamBreak3D(deltap=0.08, obstacle=False)
     arrs = prob.copy_to_array()
     f1, f2 = tmp_path / "a.bin", tmp_path / "b.bin"
     for f in (f1, f2):
         hotfile.write_hotfile(f, arrs, iterations=20, t=0.5, dt=1e-4, host_buffer_count=4)
-    r = subprocess.run([sys.executable, "/root/reference/scripts/hotdiff.py", str(f1), str(f2)],
+    r = subprocess.run([sys.executable, HOTDIFF, str(f1), str(f2)],
                        capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     for name in ("Position", "Velocity", "Info", "Hash"):
@@ -106,7 +111,7 @@ def test_reference_hotdiff_reads_our_files(tmp_path):
     # and it does see a difference when there is one
     arrs["vel"][7, 0] += 1.0
     hotfile.write_hotfile(f2, arrs, iterations=20, t=0.5, dt=1e-4, host_buffer_count=4)
-    r = subprocess.run([sys.executable, "/root/reference/scripts/hotdiff.py", str(f1), str(f2)],
+    r = subprocess.run([sys.executable, HOTDIFF, str(f1), str(f2)],
                        capture_output=True, text=True, timeout=120)
     assert "First difference at particle index 7" in r.stdout
 

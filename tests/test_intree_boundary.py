@@ -1,7 +1,7 @@
-"""The host side of the drop-in boundary, built INSIDE the GPUSPH tree (gpusph_amd/host/Makefile, target intree):
+"""The host side of the drop-in boundary, built INSIDE the GPUSPH tree (oracle/Makefile, target host, into oracle/_ref/host):
 hip_engines.h derives from the reference's own abstract engines and cudasimframework.cu stands in for the reference's
-factory under its file name.  These tests need the reference tree (present in the build container; the host programs
-are prebuilt for the GPU box) and no device.
+factory under its file name.  These tests need what build() made from the reference tree under oracle/_ref (it travels
+with oracle/_ref) and no device.
 
  * problem sources of the reference compile UNCHANGED against this repository's cudasimframework.cu
  * the frameworks the SETUP_FRAMEWORK expressions of the problems produce carry the option set of the Python problem
@@ -20,8 +20,9 @@ from gpusph_amd import defs as D
 from gpusph_amd.params import SphxParams
 from gpusph_amd.problem import DamBreak3D, StillWater, WaveTank, SABox
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src")), reason="needs the GPUSPH tree")
+ORACLE_DIR = os.path.join(hc.ROOT, "oracle")
+pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(hc.HOST_DIR, "framework_check")),
+                                reason="oracle/_ref/host not built (build() makes it where the GPUSPH tree is present)")
 
 
 def run_check(tmp_path, lines):
@@ -68,7 +69,7 @@ def test_reference_problem_sources_compile_unchanged():
           "StillWater", "WaveTank"]
     fast = os.environ.get("SPHX_ALL_PROBLEMS", "0") != "1"
     names = ["DamBreak3D", "StillWater", "WaveTank", "OpenChannel", "LockExchange"] if fast else ok
-    r = subprocess.run(["make", "-s", "-C", hc.HOST_DIR, "problems_syntax", "PROBLEMS=" + " ".join(names)],
+    r = subprocess.run(["make", "-s", "-C", ORACLE_DIR, "problems_syntax", "PROBLEMS=" + " ".join(names)],
                        capture_output=True, text=True, timeout=1800)
     assert r.returncode == 0, r.stdout + r.stderr
     for n in names:

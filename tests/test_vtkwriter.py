@@ -42,28 +42,15 @@ def test_vtp_round_trip_and_layout(tmp_path):
 def test_array_names_order_and_types_follow_the_reference_writer_source(tmp_path):
     """Not our restatement of the layout but the reference's own writer: the sequence of `appender.append_data(..., "Name"...)`
     calls of src/writers/VTKWriter.cc gives the order of the arrays in a GPUSPH file, the return types of the accessor
-    functions it passes give their element types.  Every array we write must appear there, in that order, with that type."""
-    import os, re
-    import pytest
-    src = "/root/reference/src/writers/VTKWriter.cc"
-    if not os.path.exists(src):
-        pytest.skip("needs the GPUSPH tree")
-    text = open(src).read()
-    body = text[text.index("VTKAppender appender(fid, info, gdata, node_offset, numParts);"):]
-    body = body[:body.index("</AppendedData>")] if "</AppendedData>" in body else body
-    ref_names = []
-    accessor = {}
-    calls = [m.start() for m in re.finditer(r"appender\.append_(?:local_)?data\(", body)]
-    for a, b in zip(calls, calls[1:] + [len(body)]):
-        args = body[a:b].split(";")[0].split("[")[0]            # one call: up to its ';' (or to a lambda argument)
-        names = re.findall(r'"([^"]+)"', args)
-        ref_names += names
-        fn = re.search(r",\s*(get_\w+|demote_w|id)\s*\)\s*$", args.strip())
-        if fn and names:
-            accessor[names[0]] = fn.group(1)
+    functions it passes give their element types (read off that source into tests/golden/ref_vtkwriter_layout.json by
+    tests/golden/make_golden.py).  Every array we write must appear there, in that order, with that type."""
+    import json, os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_vtkwriter_layout.json")) as f:
+        layout = json.load(f)
+    ref_names, accessor = layout["names"], layout["accessor"]
     assert ref_names[:4] == ["Position", "Neibs", "NextID", "Internal Energy"] and "CellIndex" in ref_names
     ctype = {"float": np.float32, "uchar": np.uint8, "ushort": np.uint16, "uint": np.uint32}
-    ret = {fn: ctype[t] for t, fn in re.findall(r"^(float|uchar|ushort|uint)\s+(get_\w+|demote_w)\(", text, re.M)}
+    ret = {fn: ctype[t] for fn, t in layout["returns"].items()}
     # a state with every optional array this writer knows
     from gpusph_amd.problem import SABox
     prob = DamBreak3D(deltap=0.08, obstacle=True)
