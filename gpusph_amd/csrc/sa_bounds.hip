@@ -811,6 +811,77 @@ static int sa_check(sphx_ctx *ctx, const char *who)
 	return SPHX_OK;
 }
 
+// ---- what the host side of the passes below shares ---------------------------------------------------------------------------
+// A pass over the fluid particles is up to three launches: the tiled window for the particle <- particle sums (sphx_sa_tiles_run,
+// forces.hip), the boundary-element terms with one element per lane for the particles of ctx->sa_wall (sa_wall.hip), and the
+// one-thread list walker of this file, which finishes the rows -- or is the whole pass where the other two are not to be had.
+// First the groups of pointers every argument block has:
+template <class Args> static void sa_set_lists(Args &a, const void *info, const uint32_t *hash, const uint32_t *cellStart, const uint16_t *neibsList)
+{
+	a.info = (const particleinfo*)info; a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList;
+}
+template <class Args> static void sa_set_elements(Args &a, const void *boundElements, const void *vertPos0, const void *vertPos1, const void *vertPos2)
+{
+	a.boundElement = (const float4*)boundElements;
+	a.vertPos[0] = (const float2*)vertPos0; a.vertPos[1] = (const float2*)vertPos1; a.vertPos[2] = (const float2*)vertPos2;
+}
+
+// Is there a list of wall particles for this neighbour list?  Every pass asks here before it takes sa_wall.hip's kernels.
+static bool sa_wall_ready(const sphx_ctx *ctx, const uint16_t *neibsList)
+{
+	return ctx->sa_wall && ctx->sa_wall_neibslist == neibsList;
+}
+
+// |grad gamma_as| kept from the density summation / gamma quadrature of a state for the forces pass at the same positions (a row is tagged
+// with the particle's position and the generation of the rows; what moves elements starts a new one).  gsum: see sa_forces_tiles_and_walls
+static SaWallCache sa_wall_cache(const sphx_ctx *ctx, bool gsum = false)
+{
+	return SaWallCache{ ctx->sa_wall_cache, ctx->sa_wall_tag, ctx->sa_wall_capacity, ctx->sa_wall_gen, gsum ? ctx->sa_wall_gsum : nullptr };
+}
+
+// What the tiles left for forces and density summation; true: sa_wall.hip's kernel is next.  Solid walls: `tiled` follows `used` whether
+// or not there is a list of wall particles, and tileGuard stays as returned.  Open boundaries: `tiled` only together with that list;
+// without it tileGuard = nullptr and the walker (which has the OPEN terms) is the whole pass, whatever the tiles left in FORCES.
+template <class Args> static bool sa_after_tiles(const sphx_ctx *ctx, Args &a, bool open, bool used)
+{
+	const bool wall = used && sa_wall_ready(ctx, a.neibsList);
+	a.tiled = (open ? wall : used) ? 1 : 0;
+	if (open && !wall) a.tileGuard = nullptr;
+	return wall;
+}
+
+// The wall pass of the density summation.  With open boundaries sa_density_sum_wall_kernel<true> appends the fluid particles with an
+// open segment in reach to ctx->sa_wall_open ([0] = their number) for the open faces' part of the density diffusion (sa_wall.hip):
+// the list is allocated on first use (where that fails the diffusion goes through every wall particle), emptied, valid for no neighbour
+// list during the pass and for this one after it -- unless the pass went over a part of the particles, which leaves a part of the list.
+static int sa_density_sum_walls(sphx_ctx *ctx, SaDensitySumArgs &a, bool open, bool moving, uint32_t numParticles, hipStream_t st)
+{
+	if (open) {
+		ctx->sa_wall_open_neibslist = nullptr;
+		if (!ctx->sa_wall_open && hipMalloc((void**)&ctx->sa_wall_open, sizeof(uint32_t)*((size_t)ctx->reserved_particles + 1)) != hipSuccess) {
+			(void)hipGetLastError();
+			ctx->sa_wall_open = nullptr;
+		}
+		if (ctx->sa_wall_open) {
+			SPHX_HIP(hipMemsetAsync(ctx->sa_wall_open, 0, sizeof(uint32_t), st));
+			a.openList = ctx->sa_wall_open;
+		}
+	}
+	const int rc = moving ? sphx_sa_wall_density_sum_moving(ctx, a, st) : sphx_sa_wall_density_sum(ctx, a, st);
+	if (rc == SPHX_OK && a.openList && a.numParticles == numParticles) {
+		ctx->sa_wall_open_neibslist = a.neibsList; ctx->sa_wall_open_gen = ctx->sa_wall_gen;
+	}
+	return rc;
+}
+
+// The two boundary-condition passes: where the lists of ALL boundary elements / ALL vertex particles of the build are of this
+// neighbour list and cover the range, thread t takes row t of them (SaArgs::rows); nullptr: one thread per particle
+static const uint32_t *sa_bc_rows(const sphx_ctx *ctx, const uint16_t *neibsList, uint32_t particleRangeEnd, bool vertexPass)
+{
+	if (ctx->sa_wall_neibslist != neibsList || particleRangeEnd > ctx->sa_rows_range) return nullptr;
+	return vertexPass ? ctx->sa_rows_vert : ctx->sa_rows_bound;
+}
+
 extern "C" int sphx_sa_compute_vertex_normal(sphx_ctx *ctx, void *boundElements, const void *vertices, const void *info,
 	const uint32_t *hash, const uint32_t *cellStart, const uint16_t *neibsList,
 	uint32_t numParticles, uint32_t particleRangeEnd, void *stream)
@@ -821,8 +892,8 @@ extern "C" int sphx_sa_compute_vertex_normal(sphx_ctx *ctx, void *boundElements,
 	SPHX_REQUIRE(boundElements && vertices && info && hash && cellStart && neibsList, "sphx_sa_compute_vertex_normal: missing buffer");
 	if (!particleRangeEnd) return SPHX_OK;
 	SaArgs a = {};
-	a.boundElement = (float4*)boundElements; a.vertices = (const uint4*)vertices; a.info = (const particleinfo*)info;
-	a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList; a.numParticles = particleRangeEnd;
+	a.boundElement = (float4*)boundElements; a.vertices = (const uint4*)vertices; a.numParticles = particleRangeEnd;
+	sa_set_lists(a, info, hash, cellStart, neibsList);
 	a.pos = (const float4*)boundElements;     // the walker prefetches a position row per entry; the kernel does not use it
 	sa_vertex_normal_kernel<<<div_up_u(particleRangeEnd, 128), 128, 0, (hipStream_t)stream>>>(ctx->dev, a);
 	SPHX_LAUNCH_CHECK("sa_vertex_normal_kernel");
@@ -846,11 +917,11 @@ static int sa_segment_bc_impl(sphx_ctx *ctx, void *vel, void *gGam, float *tke, 
 	if (!particleRangeEnd) return SPHX_OK;
 	SaArgs a = {};
 	a.vel = (float4*)vel; a.gGam = (float4*)gGam; a.pos = (const float4*)pos; a.vertices = (const uint4*)vertices;
-	a.boundElement = (float4*)const_cast<void*>(boundElements); a.info = (const particleinfo*)info;
-	a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList; a.numParticles = particleRangeEnd;
+	a.boundElement = (float4*)const_cast<void*>(boundElements); a.numParticles = particleRangeEnd;
+	sa_set_lists(a, info, hash, cellStart, neibsList);
 	a.step = (step == -1) ? 0 : step;         // "step -1 is the same as step 0", boundary_conditions.cu:177-180
 	a.repack = (run_mode == SPHX_REPACK);
-	if (ctx->sa_wall_neibslist == neibsList && particleRangeEnd <= ctx->sa_rows_range) a.rows = ctx->sa_rows_bound;
+	a.rows = sa_bc_rows(ctx, neibsList, particleRangeEnd, false);
 	if (tke) {
 		a.tke = tke; a.eps = eps; a.eulerVel = (float4*)eulerVel; a.deltap = deltap;
 		sa_segment_bc_kernel<SPHX_WENDLAND, true><<<div_up_u(particleRangeEnd, 128), 128, 0, (hipStream_t)stream>>>(ctx->dev, a);
@@ -898,9 +969,9 @@ static int sa_vertex_bc_impl(sphx_ctx *ctx, void *vel, const void *gGam, float *
 		"sphx_sa_vertex_bc: slength / influenceradius differ from the uploaded constants");
 	if (!particleRangeEnd) return SPHX_OK;
 	SaArgs a = {};
-	a.vel = (float4*)vel; a.gGam = (float4*)const_cast<void*>(gGam); a.pos = (const float4*)pos; a.info = (const particleinfo*)info;
-	a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList; a.numParticles = particleRangeEnd;
-	if (ctx->sa_wall_neibslist == neibsList && particleRangeEnd <= ctx->sa_rows_range) a.rows = ctx->sa_rows_vert;
+	a.vel = (float4*)vel; a.gGam = (float4*)const_cast<void*>(gGam); a.pos = (const float4*)pos; a.numParticles = particleRangeEnd;
+	sa_set_lists(a, info, hash, cellStart, neibsList);
+	a.rows = sa_bc_rows(ctx, neibsList, particleRangeEnd, true);
 	if (tke) {
 		a.tke = tke; a.eps = eps; a.eulerVel = (float4*)eulerVel;
 		a.vertices = (const uint4*)vertices; a.boundElement = (float4*)const_cast<void*>(boundElements);
@@ -950,10 +1021,9 @@ extern "C" int sphx_sa_init_gamma(sphx_ctx *ctx, void *newGGam, const void *oldG
 		"sphx_sa_init_gamma: slength / influenceradius differ from the uploaded constants");
 	if (!particleRangeEnd) return SPHX_OK;
 	SaGammaArgs a = {};
-	a.newGGam = (float4*)newGGam; a.pos = (const float4*)pos; a.boundElement = (const float4*)boundElements;
-	a.vertPos[0] = (const float2*)vertPos0; a.vertPos[1] = (const float2*)vertPos1; a.vertPos[2] = (const float2*)vertPos2;
-	a.info = (const particleinfo*)info; a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList;
-	a.numParticles = particleRangeEnd; a.deltap = deltap; a.epsilon = epsilon;
+	a.newGGam = (float4*)newGGam; a.pos = (const float4*)pos; a.numParticles = particleRangeEnd; a.deltap = deltap; a.epsilon = epsilon;
+	sa_set_elements(a, boundElements, vertPos0, vertPos1, vertPos2);
+	sa_set_lists(a, info, hash, cellStart, neibsList);
 	hipStream_t st = (hipStream_t)stream;
 	// fluid particles, then vertex particles (saInitGamma, src/cuda/boundary_conditions.cu:497-535)
 	sa_init_gamma_kernel<PT_FLUID><<<div_up_u(particleRangeEnd, 128), 128, 0, st>>>(ctx->dev, a);
@@ -991,6 +1061,36 @@ static int sa_forces_check(sphx_ctx *ctx, const char *who)
 
 struct SaKepsBuffers { float *cflKeps, *dkde; const float *tke, *eps, *turbvisc; const void *eulerVel; float epsilon; };
 
+// The fast path of the laminar forces (KEPSILON never uses the tiles), solid walls and open boundaries: the particle <- particle
+// sums through the tiled window, the boundary elements with one element per lane.  What an open boundary adds -- the Eulerian
+// velocities in the viscous terms of vertices and elements, the second gamma CFL term -- rides with the latter
+// (sa_forces_wall_kernel, a.open); the walker then only finishes the rows.
+static int sa_forces_tiles_and_walls(sphx_ctx *ctx, SaForcesArgs &a, bool open, uint32_t numParticles, hipStream_t st)
+{
+	bool used = false;
+	int rc = sphx_sa_tiles_run(ctx, SPHX_SA_TILE_FORCES, a.forces, a.pos, a.vel, nullptr, a.info, a.hash, a.cellStart, a.neibsList, a.gGam,
+		numParticles, a.fromParticle, a.toParticle, 0.0f, st, &used, &a.tileGuard);
+	if (rc != SPHX_OK) return rc;
+	if (!sa_after_tiles(ctx, a, open, used)) return SPHX_OK;
+	a.wallDone = 1; a.open = open ? 1 : 0;
+	a.wc = sa_wall_cache(ctx);
+	// wc.gsum, open boundaries only: the sum of grad gamma_as at step n for the density summations of this step, two rows per wall
+	// particle that has rows of |grad gamma_as|; allocated on first use (where that fails the density summations evaluate the elements
+	// at step n themselves).  Not with ENABLE_MOVING_BODIES, whose elements are elsewhere when those run: sphx_sa_density_sum_io
+	// hands gsum on, its moving variant does not.
+	if (open && !(ctx->params.simflags & SPHX_ENABLE_MOVING_BODIES)) {
+		const size_t bytes = sizeof(float4)*2u*ctx->sa_wall_capacity;
+		if (!ctx->sa_wall_gsum && bytes) {
+			if (hipMalloc((void**)&ctx->sa_wall_gsum, bytes) != hipSuccess) { (void)hipGetLastError(); ctx->sa_wall_gsum = nullptr; }
+			else SPHX_HIP(hipMemsetAsync(ctx->sa_wall_gsum, 0, bytes, st));
+		}
+		a.wc.gsum = ctx->sa_wall_gsum;
+	}
+	return sphx_sa_wall_forces(ctx, a, st);
+}
+
+// Solid walls: `blocks` blocks are launched and the tail of cfl, cflGamma and cflKeps up to numBlocks is zeroed; dynamic gamma with
+// ENABLE_DTADAPT requires cflGamma.  (sphx_forces_basicstep_sa_io differs in all three.)
 static int sa_forces_impl(sphx_ctx *ctx, void *forces, float *cfl, float *cflGamma, const SaKepsBuffers *ke,
 	const void *pos, const void *vel, const void *info, const uint32_t *hash, const uint32_t *cellStart, const uint16_t *neibsList,
 	const void *gGam, const void *boundElements, const void *vertPos0, const void *vertPos1, const void *vertPos2,
@@ -1020,9 +1120,8 @@ static int sa_forces_impl(sphx_ctx *ctx, void *forces, float *cfl, float *cflGam
 	if (cfl && numBlocks > blocks) SPHX_HIP(hipMemsetAsync(cfl + cflOffset + blocks, 0, sizeof(float)*(numBlocks - blocks), st));
 	SaForcesArgs a = {};
 	a.forces = (float4*)forces; a.cfl = cfl; a.pos = (const float4*)pos; a.vel = (const float4*)vel; a.gGam = (const float4*)gGam;
-	a.boundElement = (const float4*)boundElements;
-	a.vertPos[0] = (const float2*)vertPos0; a.vertPos[1] = (const float2*)vertPos1; a.vertPos[2] = (const float2*)vertPos2;
-	a.info = (const particleinfo*)info; a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList;
+	sa_set_elements(a, boundElements, vertPos0, vertPos1, vertPos2);
+	sa_set_lists(a, info, hash, cellStart, neibsList);
 	a.fromParticle = fromParticle; a.toParticle = toParticle; a.cflOffset = cflOffset; a.deltap = deltap;
 	if (run_mode == SPHX_REPACK) {
 		sa_repack_kernel<<<blocks, SPHX_BLOCK_FORCES, 0, st>>>(ctx->dev, a);
@@ -1042,20 +1141,8 @@ static int sa_forces_impl(sphx_ctx *ctx, void *forces, float *cfl, float *cflGam
 		if (ke->cflKeps && numBlocks > blocks) SPHX_HIP(hipMemsetAsync(ke->cflKeps + cflOffset + blocks, 0, sizeof(float)*(numBlocks - blocks), st));
 		sa_forces_kernel<true><<<blocks, SPHX_BLOCK_FORCES, 0, st>>>(ctx->dev, a);
 	} else {
-		bool used = false;
-		rc = sphx_sa_tiles_run(ctx, SPHX_SA_TILE_FORCES, forces, pos, vel, nullptr, info, hash, cellStart, neibsList, gGam,
-			numParticles, fromParticle, toParticle, 0.0f, st, &used, &a.tileGuard);
+		rc = sa_forces_tiles_and_walls(ctx, a, false, numParticles, st);
 		if (rc != SPHX_OK) return rc;
-		a.tiled = used ? 1 : 0;
-		if (used && ctx->sa_wall && ctx->sa_wall_neibslist == neibsList) {
-			a.wallDone = 1;
-			// |grad gamma_as| kept from the density summation of this state (a row is tagged with the particle's position and the
-			// generation of the rows; what moves elements -- a rebuild, the Euler step and the normals of a run with moving bodies --
-			// starts a new generation)
-			a.wc.values = ctx->sa_wall_cache; a.wc.tag = ctx->sa_wall_tag; a.wc.capacity = ctx->sa_wall_capacity; a.wc.gen = ctx->sa_wall_gen;
-			rc = sphx_sa_wall_forces(ctx, a, st);
-			if (rc != SPHX_OK) return rc;
-		}
 		sa_forces_kernel<false><<<blocks, SPHX_BLOCK_FORCES, 0, st>>>(ctx->dev, a);
 	}
 	SPHX_LAUNCH_CHECK("sa_forces_kernel");
@@ -1272,14 +1359,14 @@ extern "C" int sphx_sa_integrate_gamma(sphx_ctx *ctx, void *newGGam, const void 
 	if (!particleRangeEnd) return SPHX_OK;
 	SaIntGammaArgs a = {};
 	a.newGGam = (float4*)newGGam; a.oldGGam = (const float4*)oldGGam; a.pos = (const float4*)newPos;
-	a.boundElement = (const float4*)boundElements;
-	a.vertPos[0] = (const float2*)vertPos0; a.vertPos[1] = (const float2*)vertPos1; a.vertPos[2] = (const float2*)vertPos2;
-	a.info = (const particleinfo*)info; a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList;
+	sa_set_elements(a, boundElements, vertPos0, vertPos1, vertPos2);
+	sa_set_lists(a, info, hash, cellStart, neibsList);
 	a.numParticles = particleRangeEnd; a.epsilon = epsilon;
 	a.vertexRows = moving ? 1 : 0;
-	if (ctx->sa_wall && ctx->sa_wall_neibslist == neibsList && !ctx->disable_tiles && !moving) {
+	// no tiles in this pass, so the wall kernel asks for itself whether they are switched off; and it has no vertex rows
+	if (sa_wall_ready(ctx, neibsList) && !ctx->disable_tiles && !moving) {
 		a.wallDone = 1;
-		a.wc.values = ctx->sa_wall_cache; a.wc.tag = ctx->sa_wall_tag; a.wc.capacity = ctx->sa_wall_capacity; a.wc.gen = ctx->sa_wall_gen;
+		a.wc = sa_wall_cache(ctx);
 		rc = sphx_sa_wall_integrate_gamma(ctx, a, (hipStream_t)stream);
 		if (rc != SPHX_OK) return rc;
 	}
@@ -1316,6 +1403,43 @@ extern "C" int sphx_forces_dtreduce_gamma(sphx_ctx *ctx, const float *cflGamma, 
 	return rc;
 }
 
+// Density summation with dynamic gamma for the four entry points, which check their own option set and arguments: walls at rest
+// or ENABLE_MOVING_BODIES (the old and the new BUFFER_BOUNDELEMENTS, gamma of the vertex rows integrated: density_sum_impl
+// <SA_BOUNDARY>, src/cuda/euler.cu:112-160), solid walls or ENABLE_INLET_OUTLET (oldEulerVel, dt: io_gamma_contrib inside
+// computeDensitySumBoundaryTerms, src/cuda/density_sum_kernel.cu:422-484; both: the option set of CompleteSaExample.cu:46).
+// This fills the argument block and runs the fast path; the entry point then launches its instantiation of the walker.  The tiled
+// window sums particle <- particle (a moving or an open vertex like any other); the wall kernel adds the boundary elements of the
+// fluid rows -- with moving bodies both states of every element, and the vertex rows as well where there is a list of them
+// (sa_density_sum_wall_moving_kernel, wallDone = 3); with open boundaries the flux of gamma through the open segments and the
+// virtual displacement of the open vertices (sa_density_sum_wall_kernel<true>).  The flux is handed over in newVel.w, hence two
+// buffers: with newVel == oldVel an open pass skips the fast path altogether and the walker is the whole pass.
+static int sa_density_sum_begin(sphx_ctx *ctx, SaDensitySumArgs &a, bool open, bool moving, void *newVel, void *newGGam, void *forces,
+	const void *oldPos, const void *newPos, const void *oldVel, const void *oldEulerVel, const void *oldGGam,
+	const void *oldBoundElements, const void *newBoundElements,
+	const void *vertPos0, const void *vertPos1, const void *vertPos2, const void *info,
+	const uint32_t *hash, const uint32_t *cellStart, const uint16_t *neibsList,
+	uint32_t numParticles, uint32_t particleRangeEnd, float dt, hipStream_t st)
+{
+	if (!particleRangeEnd) return SPHX_OK;
+	a = {};
+	a.newVel = (float4*)newVel; a.newGGam = (float4*)newGGam; a.forces = (float4*)forces;
+	a.oldPos = (const float4*)oldPos; a.pos = (const float4*)newPos; a.oldVel = (const float4*)oldVel; a.oldGGam = (const float4*)oldGGam;
+	sa_set_elements(a, oldBoundElements, vertPos0, vertPos1, vertPos2);
+	sa_set_lists(a, info, hash, cellStart, neibsList);
+	a.numParticles = particleRangeEnd;
+	a.boundElementNew = (const float4*)newBoundElements;         // nullptr without moving bodies
+	a.oldEulerVel = (const float4*)oldEulerVel; a.dt = dt;       // nullptr, 0 with solid walls (sa_wall.hip tells the two by oldEulerVel)
+	if (open && newVel == oldVel) return SPHX_OK;
+	bool used = false;
+	int rc = sphx_sa_tiles_run(ctx, SPHX_SA_TILE_DSUM, forces, oldPos, nullptr, newPos, info, hash, cellStart, neibsList, nullptr,
+		numParticles, 0u, particleRangeEnd, 0.0f, st, &used, &a.tileGuard);
+	if (rc != SPHX_OK) return rc;
+	if (!sa_after_tiles(ctx, a, open, used)) return SPHX_OK;
+	a.wallDone = (moving && ctx->sa_wall_vert) ? 3 : 1;
+	a.wc = sa_wall_cache(ctx, open && !moving);      // gsum: see sa_forces_tiles_and_walls
+	return sa_density_sum_walls(ctx, a, open, moving, numParticles, st);
+}
+
 extern "C" int sphx_sa_density_sum(sphx_ctx *ctx, void *newVel, void *newGGam, void *forces,
 	const void *oldPos, const void *newPos, const void *oldVel, const void *oldGGam, const void *boundElements,
 	const void *vertPos0, const void *vertPos1, const void *vertPos2, const void *info,
@@ -1337,35 +1461,15 @@ extern "C" int sphx_sa_density_sum(sphx_ctx *ctx, void *newVel, void *newGGam, v
 	SPHX_REQUIRE(newGGam != oldGGam, "sphx_sa_density_sum: gamma is double buffered");
 	SPHX_REQUIRE(slength == ctx->params.slength && influenceradius == ctx->params.influenceradius,
 		"sphx_sa_density_sum: slength / influenceradius differ from the uploaded constants");
-	if (!particleRangeEnd) return SPHX_OK;
-	SaDensitySumArgs a = {};
-	a.newVel = (float4*)newVel; a.newGGam = (float4*)newGGam; a.forces = (float4*)forces;
-	a.oldPos = (const float4*)oldPos; a.pos = (const float4*)newPos; a.oldVel = (const float4*)oldVel; a.oldGGam = (const float4*)oldGGam;
-	a.boundElement = (const float4*)boundElements;
-	a.vertPos[0] = (const float2*)vertPos0; a.vertPos[1] = (const float2*)vertPos1; a.vertPos[2] = (const float2*)vertPos2;
-	a.info = (const particleinfo*)info; a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList; a.numParticles = particleRangeEnd;
-	{
-		bool used = false;
-		rc = sphx_sa_tiles_run(ctx, SPHX_SA_TILE_DSUM, forces, oldPos, nullptr, newPos, info, hash, cellStart, neibsList, nullptr,
-			numParticles, 0u, particleRangeEnd, 0.0f, (hipStream_t)stream, &used, &a.tileGuard);
-		if (rc != SPHX_OK) return rc;
-		a.tiled = used ? 1 : 0;
-		if (used && ctx->sa_wall && ctx->sa_wall_neibslist == neibsList) {
-			a.wallDone = 1;
-			a.wc.values = ctx->sa_wall_cache; a.wc.tag = ctx->sa_wall_tag; a.wc.capacity = ctx->sa_wall_capacity; a.wc.gen = ctx->sa_wall_gen;
-			rc = sphx_sa_wall_density_sum(ctx, a, (hipStream_t)stream);
-			if (rc != SPHX_OK) return rc;
-		}
-	}
+	SaDensitySumArgs a;
+	rc = sa_density_sum_begin(ctx, a, false, false, newVel, newGGam, forces, oldPos, newPos, oldVel, nullptr, oldGGam, boundElements, nullptr,
+		vertPos0, vertPos1, vertPos2, info, hash, cellStart, neibsList, numParticles, particleRangeEnd, 0.0f, (hipStream_t)stream);
+	if (rc != SPHX_OK || !particleRangeEnd) return rc;
 	sa_density_sum_kernel<false><<<div_up_u(particleRangeEnd, 128), 128, 0, (hipStream_t)stream>>>(ctx->dev, a);
 	SPHX_LAUNCH_CHECK("sa_density_sum_kernel");
 	return SPHX_OK;
 }
 
-// density_sum with ENABLE_MOVING_BODIES (density_sum_impl<SA_BOUNDARY>, src/cuda/euler.cu:112-160): the old and the new
-// BUFFER_BOUNDELEMENTS (the read and the write list of the reference's call hold one each), fluid rows as sphx_sa_density_sum,
-// gamma of the vertex rows integrated, boundary rows untouched.  The list walker is the whole pass (the tiled window sums and
-// the wave-per-wall-particle kernels assume elements at rest).
 extern "C" int sphx_sa_density_sum_moving(sphx_ctx *ctx, void *newVel, void *newGGam, void *forces,
 	const void *oldPos, const void *newPos, const void *oldVel, const void *oldGGam,
 	const void *oldBoundElements, const void *newBoundElements,
@@ -1373,7 +1477,6 @@ extern "C" int sphx_sa_density_sum_moving(sphx_ctx *ctx, void *newVel, void *new
 	const uint32_t *hash, const uint32_t *cellStart, const uint16_t *neibsList,
 	uint32_t numParticles, uint32_t particleRangeEnd, void *stream)
 {
-	(void)numParticles;
 	int rc = sa_check(ctx, "density_sum called without SA_BOUNDARY");
 	if (rc != SPHX_OK) return rc;
 	if (!(ctx->params.simflags & SPHX_ENABLE_DENSITY_SUM) || (ctx->params.simflags & SPHX_ENABLE_GAMMA_QUADRATURE))
@@ -1385,32 +1488,47 @@ extern "C" int sphx_sa_density_sum_moving(sphx_ctx *ctx, void *newVel, void *new
 	SPHX_REQUIRE(newVel && newGGam && forces && oldPos && newPos && oldVel && oldGGam && oldBoundElements && newBoundElements &&
 		vertPos0 && vertPos1 && vertPos2 && info && hash && cellStart && neibsList, "sphx_sa_density_sum_moving: missing buffer");
 	SPHX_REQUIRE(newGGam != oldGGam && oldBoundElements != newBoundElements, "sphx_sa_density_sum_moving: gamma and the boundary elements are double buffered");
-	if (!particleRangeEnd) return SPHX_OK;
-	SaDensitySumArgs a = {};
-	a.newVel = (float4*)newVel; a.newGGam = (float4*)newGGam; a.forces = (float4*)forces;
-	a.oldPos = (const float4*)oldPos; a.pos = (const float4*)newPos; a.oldVel = (const float4*)oldVel; a.oldGGam = (const float4*)oldGGam;
-	a.boundElement = (const float4*)oldBoundElements; a.boundElementNew = (const float4*)newBoundElements;
-	a.vertPos[0] = (const float2*)vertPos0; a.vertPos[1] = (const float2*)vertPos1; a.vertPos[2] = (const float2*)vertPos2;
-	a.info = (const particleinfo*)info; a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList; a.numParticles = particleRangeEnd;
-	{
-		// the particle <- particle sums (fluid and vertex neighbours, the moving vertices with their own displacement like any other
-		// particle) through the tiled window as for walls at rest (round 6)
-		bool used = false;
-		rc = sphx_sa_tiles_run(ctx, SPHX_SA_TILE_DSUM, forces, oldPos, nullptr, newPos, info, hash, cellStart, neibsList, nullptr,
-			numParticles, 0u, particleRangeEnd, 0.0f, (hipStream_t)stream, &used, &a.tileGuard);
-		if (rc != SPHX_OK) return rc;
-		a.tiled = used ? 1 : 0;
-		// ... and the boundary-element terms of the fluid particles next to a wall with one element per lane, both states of
-		// every element (sa_density_sum_wall_moving_kernel); the vertex rows and a run without tiles stay with the walker below
-		if (used && ctx->sa_wall && ctx->sa_wall_neibslist == neibsList) {
-			a.wallDone = ctx->sa_wall_vert ? 3 : 1;
-			a.wc.values = ctx->sa_wall_cache; a.wc.tag = ctx->sa_wall_tag; a.wc.capacity = ctx->sa_wall_capacity; a.wc.gen = ctx->sa_wall_gen;
-			rc = sphx_sa_wall_density_sum_moving(ctx, a, (hipStream_t)stream);
-			if (rc != SPHX_OK) return rc;
-		}
-	}
+	SaDensitySumArgs a;
+	rc = sa_density_sum_begin(ctx, a, false, true, newVel, newGGam, forces, oldPos, newPos, oldVel, nullptr, oldGGam, oldBoundElements, newBoundElements,
+		vertPos0, vertPos1, vertPos2, info, hash, cellStart, neibsList, numParticles, particleRangeEnd, 0.0f, (hipStream_t)stream);
+	if (rc != SPHX_OK || !particleRangeEnd) return rc;
 	sa_density_sum_kernel<false, true><<<div_up_u(particleRangeEnd, 128), 128, 0, (hipStream_t)stream>>>(ctx->dev, a);
 	SPHX_LAUNCH_CHECK("sa_density_sum_kernel<moving>");
+	return SPHX_OK;
+}
+
+// Brezzi density diffusion, solid walls or open boundaries (there the segments of the pressure-driven open faces take part:
+// boundElements, vertPos, deltap).  The fluid <- fluid sum goes through the tiled window (SPHX_SA_TILE_DIFF finishes the row:
+// / gamma / rho0); the open segments add theirs to it with one element per lane (sa_wall.hip).  Where the host has seen the tiling
+// succeed (no tileGuard) there is no stand-by launch of the walker: solid walls return when the tiles were used, open boundaries
+// only when there is a list of wall particles as well -- without it the walker is the whole pass, whatever the tiles left in FORCES.w.
+// This fills the argument block and runs the fast path; *walker: the entry point is to launch its instantiation of the walker.
+static int sa_density_diffusion_begin(sphx_ctx *ctx, SaDiffusionArgs &a, bool *walker, bool open, void *forces, const void *pos, const void *vel, const void *gGam,
+	const void *boundElements, const void *vertPos0, const void *vertPos1, const void *vertPos2, const void *info,
+	const uint32_t *hash, const uint32_t *cellStart, const uint16_t *neibsList,
+	uint32_t numParticles, uint32_t particleRangeEnd, float deltap, float dt, hipStream_t st)
+{
+	*walker = false;
+	if (!particleRangeEnd) return SPHX_OK;
+	a = {};
+	a.forces = (float4*)forces; a.pos = (const float4*)pos; a.vel = (const float4*)vel; a.gGam = (const float4*)gGam;
+	sa_set_lists(a, info, hash, cellStart, neibsList);
+	a.numParticles = particleRangeEnd; a.dt = dt;
+	sa_set_elements(a, boundElements, vertPos0, vertPos1, vertPos2); a.deltap = deltap;      // nullptr, 0 with solid walls
+	bool used = false;
+	int rc = sphx_sa_tiles_run(ctx, SPHX_SA_TILE_DIFF, forces, pos, vel, nullptr, info, hash, cellStart, neibsList, gGam,
+		numParticles, 0u, particleRangeEnd, dt, st, &used, &a.tileGuard);
+	if (rc != SPHX_OK) return rc;
+	if (!open)
+		*walker = !(used && !a.tileGuard);
+	else if (used && sa_wall_ready(ctx, neibsList)) {
+		rc = sphx_sa_wall_density_diffusion_open(ctx, a, st);
+		if (rc != SPHX_OK) return rc;
+		*walker = a.tileGuard != nullptr;
+	} else {
+		a.tileGuard = nullptr;
+		*walker = true;
+	}
 	return SPHX_OK;
 }
 
@@ -1427,18 +1545,11 @@ extern "C" int sphx_sa_compute_density_diffusion(sphx_ctx *ctx, void *forces, co
 	SPHX_REQUIRE(forces && pos && vel && gGam && info && hash && cellStart && neibsList, "sphx_sa_compute_density_diffusion: missing buffer");
 	SPHX_REQUIRE(slength == ctx->params.slength && influenceradius == ctx->params.influenceradius,
 		"sphx_sa_compute_density_diffusion: slength / influenceradius differ from the uploaded constants");
-	if (!particleRangeEnd) return SPHX_OK;
-	SaDiffusionArgs a = {};
-	a.forces = (float4*)forces; a.pos = (const float4*)pos; a.vel = (const float4*)vel; a.gGam = (const float4*)gGam;
-	a.info = (const particleinfo*)info; a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList;
-	a.numParticles = particleRangeEnd; a.dt = dt;
-	{
-		bool used = false;
-		rc = sphx_sa_tiles_run(ctx, SPHX_SA_TILE_DIFF, forces, pos, vel, nullptr, info, hash, cellStart, neibsList, gGam,
-			numParticles, 0u, particleRangeEnd, dt, (hipStream_t)stream, &used, &a.tileGuard);
-		if (rc != SPHX_OK) return rc;
-		if (used && !a.tileGuard) return SPHX_OK;      // the host has seen the tiling succeed: no stand-by launch
-	}
+	SaDiffusionArgs a;
+	bool walker;
+	rc = sa_density_diffusion_begin(ctx, a, &walker, false, forces, pos, vel, gGam, nullptr, nullptr, nullptr, nullptr, info, hash, cellStart, neibsList,
+		numParticles, particleRangeEnd, 0.0f, dt, (hipStream_t)stream);
+	if (rc != SPHX_OK || !walker) return rc;
 	sa_density_diffusion_kernel<false><<<div_up_u(particleRangeEnd, 128), 128, 0, (hipStream_t)stream>>>(ctx->dev, a);
 	SPHX_LAUNCH_CHECK("sa_density_diffusion_kernel");
 	return SPHX_OK;
@@ -1458,12 +1569,16 @@ extern "C" int sphx_apply_density_diffusion(sphx_ctx *ctx, void *vel, const void
 }
 
 // ==========================================================================================
-// A run with open boundaries (SA_BOUNDARY + ENABLE_INLET_OUTLET, laminar): the passes over the FLUID particles.  They are the list
-// walkers above with their OPEN terms (the tiled window and the wave-per-wall-particle kernels do not know those terms, so the
-// walkers are the whole pass here); the passes over the elements of the open faces themselves are sa_io.hip's.
+// A run with open boundaries (SA_BOUNDARY + ENABLE_INLET_OUTLET, laminar): the passes over the FLUID particles.  They are the
+// passes above with the OPEN terms, on the same fast path: the tiled window sums particle <- particle as for solid walls (an open
+// vertex like any vertex), and sa_wall.hip's kernels, one boundary element per lane, add the open faces' terms with the
+// elements'.  The list walker with its OPEN terms finishes the rows; it is the whole pass only when the tiling overflowed, when
+// there is no list of wall particles for the neighbour list, or (density summation) when newVel == oldVel.  The passes over the
+// elements of the open faces themselves are sa_io.hip's.
 //   density_sum       src/cuda/density_sum_kernel.cu:119-140,206-250,374-420,606-655
 //   forces            src/cuda/forces_kernel.def:1485-1497,2494-2507,2703-2708
 //   density diffusion src/cuda/forces_kernel.def:1836-1852,4536-4582
+// (The one-thread density summation was 49 % of a step of the SAChannelIO mirror at 8.6 M particles, profiles/r06_sa_io_kernel_stats.txt.)
 // ==========================================================================================
 static int sa_open_check(sphx_ctx *ctx, const char *who)
 {
@@ -1477,7 +1592,7 @@ static int sa_open_check(sphx_ctx *ctx, const char *who)
 int sphx_sa_solid_rows_launch(sphx_ctx *ctx, const SaArgs &a_, bool vertexPass, hipStream_t st)
 {
 	SaArgs a = a_;
-	if (ctx->sa_wall_neibslist == a.neibsList && a.numParticles <= ctx->sa_rows_range) a.rows = vertexPass ? ctx->sa_rows_vert : ctx->sa_rows_bound;
+	a.rows = sa_bc_rows(ctx, a.neibsList, a.numParticles, vertexPass);
 	if (vertexPass) sa_vertex_bc_kernel<SPHX_WENDLAND, false><<<div_up_u(a.numParticles, 128), 128, 0, st>>>(ctx->dev, a);
 	else sa_segment_bc_kernel<SPHX_WENDLAND, false><<<div_up_u(a.numParticles, 128), 128, 0, st>>>(ctx->dev, a);
 	SPHX_LAUNCH_CHECK("sa_segment_bc_kernel / sa_vertex_bc_kernel (solid rows of a run with open boundaries)");
@@ -1494,54 +1609,15 @@ extern "C" int sphx_sa_density_sum_io(sphx_ctx *ctx, void *newVel, void *newGGam
 	if (rc != SPHX_OK) return rc;
 	SPHX_REQUIRE(newVel && newGGam && forces && oldPos && newPos && oldVel && oldEulerVel && oldGGam && boundElements && vertPos0 && vertPos1 &&
 		vertPos2 && info && hash && cellStart && neibsList, "sphx_sa_density_sum_io: missing buffer");
-	if (!particleRangeEnd) return SPHX_OK;
-	SaDensitySumArgs a = {};
-	a.newVel = (float4*)newVel; a.newGGam = (float4*)newGGam; a.forces = (float4*)forces;
-	a.oldPos = (const float4*)oldPos; a.pos = (const float4*)newPos; a.oldVel = (const float4*)oldVel; a.oldGGam = (const float4*)oldGGam;
-	a.boundElement = (const float4*)boundElements;
-	a.vertPos[0] = (const float2*)vertPos0; a.vertPos[1] = (const float2*)vertPos1; a.vertPos[2] = (const float2*)vertPos2;
-	a.info = (const particleinfo*)info; a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList; a.numParticles = particleRangeEnd;
-	a.oldEulerVel = (const float4*)oldEulerVel; a.dt = dt;
-	if (newVel != oldVel) {
-		// round 6: the particle <- particle sums through the tiled window as for solid walls (an open vertex summed like any vertex),
-		// the boundary elements with one element per lane; what the open faces change -- the flux of gamma through their segments,
-		// the virtual displacement of their vertices -- rides with the latter (sa_density_sum_wall_kernel<true>, sa_wall.hip), which
-		// hands the flux over in newVel.w (hence two buffers).  The one-thread kernel was 49 % of a step of the SAChannelIO mirror at
-		// 8.6 M particles (profiles/r06_sa_io_kernel_stats.txt)
-		bool used = false;
-		rc = sphx_sa_tiles_run(ctx, SPHX_SA_TILE_DSUM, forces, oldPos, nullptr, newPos, info, hash, cellStart, neibsList, nullptr,
-			numParticles, 0u, particleRangeEnd, 0.0f, (hipStream_t)stream, &used, &a.tileGuard);
-		if (rc != SPHX_OK) return rc;
-		if (used && ctx->sa_wall && ctx->sa_wall_neibslist == neibsList) {
-			a.tiled = 1; a.wallDone = 1;
-			a.wc.values = ctx->sa_wall_cache; a.wc.tag = ctx->sa_wall_tag; a.wc.capacity = ctx->sa_wall_capacity; a.wc.gen = ctx->sa_wall_gen;
-			a.wc.gsum = ctx->sa_wall_gsum;
-			ctx->sa_wall_open_neibslist = nullptr;
-			if (!ctx->sa_wall_open && hipMalloc((void**)&ctx->sa_wall_open, sizeof(uint32_t)*((size_t)ctx->reserved_particles + 1)) != hipSuccess) {
-				(void)hipGetLastError();
-				ctx->sa_wall_open = nullptr;      // the diffusion goes through every wall particle then
-			}
-			if (ctx->sa_wall_open) {
-				SPHX_HIP(hipMemsetAsync(ctx->sa_wall_open, 0, sizeof(uint32_t), (hipStream_t)stream));
-				a.openList = ctx->sa_wall_open;
-			}
-			rc = sphx_sa_wall_density_sum(ctx, a, (hipStream_t)stream);
-			if (rc != SPHX_OK) return rc;
-			if (ctx->sa_wall_open && particleRangeEnd == numParticles) {      // (a pass over a part of the particles leaves a part of the list)
-				ctx->sa_wall_open_neibslist = neibsList; ctx->sa_wall_open_gen = ctx->sa_wall_gen;
-			}
-		} else
-			a.tileGuard = nullptr;      // (no list of wall particles: the walker is the whole pass, whatever the tiles left in FORCES.w)
-	}
+	SaDensitySumArgs a;
+	rc = sa_density_sum_begin(ctx, a, true, false, newVel, newGGam, forces, oldPos, newPos, oldVel, oldEulerVel, oldGGam, boundElements, nullptr,
+		vertPos0, vertPos1, vertPos2, info, hash, cellStart, neibsList, numParticles, particleRangeEnd, dt, (hipStream_t)stream);
+	if (rc != SPHX_OK || !particleRangeEnd) return rc;
 	sa_density_sum_kernel<true><<<div_up_u(particleRangeEnd, 128), 128, 0, (hipStream_t)stream>>>(ctx->dev, a);
 	SPHX_LAUNCH_CHECK("sa_density_sum_kernel<open>");
 	return SPHX_OK;
 }
 
-// ENABLE_INLET_OUTLET | ENABLE_DENSITY_SUM | ENABLE_MOVING_BODIES, the option set of CompleteSaExample.cu (:46): the open faces'
-// terms of sphx_sa_density_sum_io in the boundary loop of sphx_sa_density_sum_moving (io_gamma_contrib inside
-// computeDensitySumBoundaryTerms, src/cuda/density_sum_kernel.cu:422-484) -- elements where they were and where they are, gamma
-// of the VERTEX rows integrated, the virtual displacement of the open vertices and segments in the sums of the fluid
 extern "C" int sphx_sa_density_sum_io_moving(sphx_ctx *ctx, void *newVel, void *newGGam, void *forces, const void *oldPos, const void *newPos,
 	const void *oldVel, const void *oldEulerVel, const void *oldGGam, const void *oldBoundElements, const void *newBoundElements,
 	const void *vertPos0, const void *vertPos1, const void *vertPos2, const void *info,
@@ -1555,47 +1631,17 @@ extern "C" int sphx_sa_density_sum_io_moving(sphx_ctx *ctx, void *newVel, void *
 	SPHX_REQUIRE(newVel && newGGam && forces && oldPos && newPos && oldVel && oldEulerVel && oldGGam && oldBoundElements && newBoundElements &&
 		vertPos0 && vertPos1 && vertPos2 && info && hash && cellStart && neibsList, "sphx_sa_density_sum_io_moving: missing buffer");
 	SPHX_REQUIRE(newGGam != oldGGam && oldBoundElements != newBoundElements, "sphx_sa_density_sum_io_moving: gamma and the boundary elements are double buffered");
-	if (!particleRangeEnd) return SPHX_OK;
-	SaDensitySumArgs a = {};
-	a.newVel = (float4*)newVel; a.newGGam = (float4*)newGGam; a.forces = (float4*)forces;
-	a.oldPos = (const float4*)oldPos; a.pos = (const float4*)newPos; a.oldVel = (const float4*)oldVel; a.oldGGam = (const float4*)oldGGam;
-	a.boundElement = (const float4*)oldBoundElements; a.boundElementNew = (const float4*)newBoundElements;
-	a.vertPos[0] = (const float2*)vertPos0; a.vertPos[1] = (const float2*)vertPos1; a.vertPos[2] = (const float2*)vertPos2;
-	a.info = (const particleinfo*)info; a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList; a.numParticles = particleRangeEnd;
-	a.oldEulerVel = (const float4*)oldEulerVel; a.dt = dt;
-	if (newVel != oldVel) {
-		// round 6: as sphx_sa_density_sum_io and sphx_sa_density_sum_moving -- the particle <- particle sums through the tiled window, the
-		// boundary-element terms of the fluid rows (with the open faces' terms) and of the vertex rows with one element per lane
-		// (sa_density_sum_wall_moving_kernel<true>); the flux of gamma rides in newVel.w, hence two buffers
-		bool used = false;
-		rc = sphx_sa_tiles_run(ctx, SPHX_SA_TILE_DSUM, forces, oldPos, nullptr, newPos, info, hash, cellStart, neibsList, nullptr,
-			numParticles, 0u, particleRangeEnd, 0.0f, (hipStream_t)stream, &used, &a.tileGuard);
-		if (rc != SPHX_OK) return rc;
-		if (used && ctx->sa_wall && ctx->sa_wall_neibslist == neibsList) {
-			a.tiled = 1; a.wallDone = ctx->sa_wall_vert ? 3 : 1;
-			a.wc.values = ctx->sa_wall_cache; a.wc.tag = ctx->sa_wall_tag; a.wc.capacity = ctx->sa_wall_capacity; a.wc.gen = ctx->sa_wall_gen;
-			ctx->sa_wall_open_neibslist = nullptr;
-			if (!ctx->sa_wall_open && hipMalloc((void**)&ctx->sa_wall_open, sizeof(uint32_t)*((size_t)ctx->reserved_particles + 1)) != hipSuccess) {
-				(void)hipGetLastError();
-				ctx->sa_wall_open = nullptr;
-			}
-			if (ctx->sa_wall_open) {
-				SPHX_HIP(hipMemsetAsync(ctx->sa_wall_open, 0, sizeof(uint32_t), (hipStream_t)stream));
-				a.openList = ctx->sa_wall_open;
-			}
-			rc = sphx_sa_wall_density_sum_moving(ctx, a, (hipStream_t)stream);
-			if (rc != SPHX_OK) return rc;
-			if (ctx->sa_wall_open && particleRangeEnd == numParticles) {
-				ctx->sa_wall_open_neibslist = neibsList; ctx->sa_wall_open_gen = ctx->sa_wall_gen;
-			}
-		} else
-			a.tileGuard = nullptr;      // (no list of wall particles: the walker is the whole pass, whatever the tiles left in FORCES.w)
-	}
+	SaDensitySumArgs a;
+	rc = sa_density_sum_begin(ctx, a, true, true, newVel, newGGam, forces, oldPos, newPos, oldVel, oldEulerVel, oldGGam, oldBoundElements, newBoundElements,
+		vertPos0, vertPos1, vertPos2, info, hash, cellStart, neibsList, numParticles, particleRangeEnd, dt, (hipStream_t)stream);
+	if (rc != SPHX_OK || !particleRangeEnd) return rc;
 	sa_density_sum_kernel<true, true><<<div_up_u(particleRangeEnd, 128), 128, 0, (hipStream_t)stream>>>(ctx->dev, a);
 	SPHX_LAUNCH_CHECK("sa_density_sum_kernel<open, moving>");
 	return SPHX_OK;
 }
 
+// Open boundaries: numBlocks blocks are launched (the rounded-up count), nothing is zeroed, and a null cflGamma means "no gamma CFL".
+// (sa_forces_impl differs in all three.)
 extern "C" int sphx_forces_basicstep_sa_io(sphx_ctx *ctx, void *forces, float *cfl, float *cflGamma, const void *pos, const void *vel,
 	const void *eulerVel, const void *info, const uint32_t *hash, const uint32_t *cellStart, const uint16_t *neibsList,
 	const void *gGam, const void *boundElements, const void *vertPos0, const void *vertPos1, const void *vertPos2,
@@ -1616,39 +1662,11 @@ extern "C" int sphx_forces_basicstep_sa_io(sphx_ctx *ctx, void *forces, float *c
 	a.forces = (float4*)forces; a.cfl = dtadapt ? cfl : nullptr;
 	a.cflGamma = gcfl ? cflGamma : nullptr; a.cflGammaBlocks = gcfl ? cflGamma + round_up_u(numParticles, 4u) : nullptr;
 	a.pos = (const float4*)pos; a.vel = (const float4*)vel; a.eulerVel = (const float4*)eulerVel; a.gGam = (const float4*)gGam;
-	a.boundElement = (const float4*)boundElements;
-	a.vertPos[0] = (const float2*)vertPos0; a.vertPos[1] = (const float2*)vertPos1; a.vertPos[2] = (const float2*)vertPos2;
-	a.info = (const particleinfo*)info; a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList;
+	sa_set_elements(a, boundElements, vertPos0, vertPos1, vertPos2);
+	sa_set_lists(a, info, hash, cellStart, neibsList);
 	a.fromParticle = fromParticle; a.toParticle = toParticle; a.cflOffset = cflOffset; a.deltap = deltap;
-	{
-		// round 6: the particle <- particle sums through the tiled window as for solid walls, the boundary elements with one element
-		// per lane; what an open boundary adds -- the Eulerian velocities in the viscous terms of vertices and elements, the second
-		// gamma CFL term -- rides with the latter (sa_forces_wall_kernel, a.open); this kernel then only finishes the rows
-		bool used = false;
-		rc = sphx_sa_tiles_run(ctx, SPHX_SA_TILE_FORCES, forces, pos, vel, nullptr, info, hash, cellStart, neibsList, gGam,
-			numParticles, fromParticle, toParticle, 0.0f, (hipStream_t)stream, &used, &a.tileGuard);
-		if (rc != SPHX_OK) return rc;
-		if (used && ctx->sa_wall && ctx->sa_wall_neibslist == neibsList) {
-			a.tiled = 1; a.wallDone = 1; a.open = 1;
-			a.wc.values = ctx->sa_wall_cache; a.wc.tag = ctx->sa_wall_tag; a.wc.capacity = ctx->sa_wall_capacity; a.wc.gen = ctx->sa_wall_gen;
-			// (the sum of grad gamma_as at step n for the density summations of this step -- not with moving bodies, whose elements are
-			// elsewhere when those run)
-			if (!(ctx->params.simflags & SPHX_ENABLE_MOVING_BODIES)) {
-				if (!ctx->sa_wall_gsum && ctx->sa_wall_capacity) {      // two rows per wall particle that has rows of |grad gamma_as|
-					if (hipMalloc((void**)&ctx->sa_wall_gsum, sizeof(float4)*2u*ctx->sa_wall_capacity) == hipSuccess)
-						SPHX_HIP(hipMemsetAsync(ctx->sa_wall_gsum, 0, sizeof(float4)*2u*ctx->sa_wall_capacity, (hipStream_t)stream));
-					else {
-						(void)hipGetLastError();
-						ctx->sa_wall_gsum = nullptr;      // the density summations evaluate the elements at step n themselves
-					}
-				}
-				a.wc.gsum = ctx->sa_wall_gsum;
-			}
-			rc = sphx_sa_wall_forces(ctx, a, (hipStream_t)stream);
-			if (rc != SPHX_OK) return rc;
-		} else
-			a.tileGuard = nullptr;      // (no list of wall particles: the walker is the whole pass)
-	}
+	rc = sa_forces_tiles_and_walls(ctx, a, true, numParticles, (hipStream_t)stream);
+	if (rc != SPHX_OK) return rc;
 	sa_forces_kernel<false, true><<<numBlocks, SPHX_BLOCK_FORCES, 0, (hipStream_t)stream>>>(ctx->dev, a);
 	SPHX_LAUNCH_CHECK("sa_forces_kernel<open>");
 	return SPHX_OK;
@@ -1659,7 +1677,6 @@ extern "C" int sphx_sa_compute_density_diffusion_io(sphx_ctx *ctx, void *forces,
 	const uint32_t *hash, const uint32_t *cellStart, const uint16_t *neibsList,
 	uint32_t numParticles, uint32_t particleRangeEnd, float deltap, float dt, void *stream)
 {
-	(void)numParticles;
 	int rc = sa_open_check(ctx, "compute_density_diffusion called without SA_BOUNDARY");
 	if (rc != SPHX_OK) return rc;
 	if (ctx->params.densitydiffusiontype != SPHX_BREZZI || !(ctx->params.simflags & SPHX_ENABLE_DENSITY_SUM) ||
@@ -1667,29 +1684,11 @@ extern "C" int sphx_sa_compute_density_diffusion_io(sphx_ctx *ctx, void *forces,
 		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx_sa_compute_density_diffusion_io: built for Brezzi diffusion with density summation");
 	SPHX_REQUIRE(forces && pos && vel && gGam && boundElements && vertPos0 && vertPos1 && vertPos2 && info && hash && cellStart && neibsList,
 		"sphx_sa_compute_density_diffusion_io: missing buffer");
-	if (!particleRangeEnd) return SPHX_OK;
-	SaDiffusionArgs a = {};
-	a.forces = (float4*)forces; a.pos = (const float4*)pos; a.vel = (const float4*)vel; a.gGam = (const float4*)gGam;
-	a.info = (const particleinfo*)info; a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList;
-	a.numParticles = particleRangeEnd; a.dt = dt;
-	a.boundElement = (const float4*)boundElements;
-	a.vertPos[0] = (const float2*)vertPos0; a.vertPos[1] = (const float2*)vertPos1; a.vertPos[2] = (const float2*)vertPos2; a.deltap = deltap;
-	{
-		// the fluid <- fluid sum is the solid-wall one: through the tiled window (SPHX_SA_TILE_DIFF finishes the row: / gamma / rho0);
-		// the segments of the pressure-driven open faces add theirs to it with one element per lane (sa_wall.hip).  Round 6: such a run
-		// rebuilds its lists in every step, and the tile lists of one rebuild cost a tenth of what the list walkers of one step did
-		// (profiles/r06_sa_io_kernel_stats.txt)
-		bool used = false;
-		rc = sphx_sa_tiles_run(ctx, SPHX_SA_TILE_DIFF, forces, pos, vel, nullptr, info, hash, cellStart, neibsList, gGam,
-			numParticles, 0u, particleRangeEnd, dt, (hipStream_t)stream, &used, &a.tileGuard);
-		if (rc != SPHX_OK) return rc;
-		if (used && ctx->sa_wall && ctx->sa_wall_neibslist == neibsList) {
-			rc = sphx_sa_wall_density_diffusion_open(ctx, a, (hipStream_t)stream);
-			if (rc != SPHX_OK) return rc;
-			if (!a.tileGuard) return SPHX_OK;      // the host has seen the tiling succeed: no stand-by launch
-		} else
-			a.tileGuard = nullptr;      // (no list of wall particles: the walker is the whole pass, whatever the tiles left in FORCES.w)
-	}
+	SaDiffusionArgs a;
+	bool walker;
+	rc = sa_density_diffusion_begin(ctx, a, &walker, true, forces, pos, vel, gGam, boundElements, vertPos0, vertPos1, vertPos2, info, hash, cellStart, neibsList,
+		numParticles, particleRangeEnd, deltap, dt, (hipStream_t)stream);
+	if (rc != SPHX_OK || !walker) return rc;
 	sa_density_diffusion_kernel<true><<<div_up_u(particleRangeEnd, 128), 128, 0, (hipStream_t)stream>>>(ctx->dev, a);
 	SPHX_LAUNCH_CHECK("sa_density_diffusion_kernel<open>");
 	return SPHX_OK;

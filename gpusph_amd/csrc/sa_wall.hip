@@ -142,6 +142,8 @@ __device__ __forceinline__ bool wall_gsum_get(const SaWallCache &wc, uint32_t w,
 }
 
 // the fluid <- boundary-element part of sa_forces_kernel<false> (same terms, see there), added to the sums the tiled kernel left
+// a.open: the Eulerian part of the fluid <- vertex viscous term as well.  ASSUMED, not checked: a fluid particle with an open vertex in
+// reach has a segment in reach too (see sa_density_sum_wall_kernel<true>); one that has not keeps the solid-wall tiled sums.
 __global__ void __launch_bounds__(SA_WALL_THREADS)
 sa_forces_wall_kernel(DevParams p, SaForcesArgs a, const uint32_t *__restrict__ wall)
 {
@@ -292,6 +294,10 @@ sa_forces_wall_kernel(DevParams p, SaForcesArgs a, const uint32_t *__restrict__ 
 //  * a vertex of an open face is not a reservoir of mass at rest: the tiled kernel has summed -m W(r_n) for it as for any
 //    neighbour; that term is taken back here and the kernel at the distance after the virtual displacement put in its place
 //    (FORCES.w, which holds the tiled sums).
+// ASSUMED, not checked: a fluid particle with an open vertex in reach has a segment in reach too, so that it is in ctx->sa_wall and this
+// kernel sees it; one that has not keeps the solid-wall tiled sum for that vertex.  True for meshes whose elements have the size of
+// deltap, as those of the test problems (the boundary section is built out to boundNlSqInflRad, further than the vertex section);
+// a coarse or irregular mesh may break it.
 template<bool OPEN>
 __global__ void __launch_bounds__(SA_WALL_THREADS)
 sa_density_sum_wall_kernel(DevParams p, SaDensitySumArgs a, const uint32_t *__restrict__ wall)
