@@ -1958,8 +1958,8 @@ static int launch_forces_k(const sphx_ctx *ctx, dim3 grid, hipStream_t stream, c
 	const bool mf = p.numfluids > 1;
 	const int diff = (p.densitydiff == SPHX_COLAGROSSI) ? DIFF_COLAGROSSI : (p.densitydiff == SPHX_FERRARI) ? DIFF_FERRARI : DIFF_NONE;
 	const bool newt = p.rheology == SPHX_NEWTONIAN;
-	const uint32_t *guard = use_tiles ? ctx->tile_ctl + 1 : nullptr;
-	const bool standby = !use_tiles || ctx->tiles_overflow != 0;   // the host saw the tiling succeed (sphx_neibs_getinfo): no stand-by launch
+	const uint32_t *guard = use_tiles ? sphx_tiles_standby_guard(ctx) : nullptr;
+	const bool standby = !use_tiles || guard;   // the host saw the tiling succeed: no stand-by launch
 	ForcesTimer t(ctx, stream, !use_tiles);   // without tiles the generic kernel is the dominant one
 	// tiled kernel, then the generic one, guarded by the overflow flag
 	// more than one fluid or Ferrari diffusion: tiled only for the Wendland kernel (every such problem of the reference uses
@@ -2495,7 +2495,7 @@ int sphx_tile_lists_launch(sphx_ctx *ctx, const uint16_t *neibsList, const void 
 	uint32_t homeFrom, uint32_t homeTo)
 {
 	if (!ctx->tile_list || !ctx->tile_runs || !ctx->tile_rows || !ctx->tile_lane_rec || !ctx->tile_lane_index || !ctx->neib_counts) {
-		ctx->tiles_built = false;
+		sphx_tiles_invalidate(ctx);
 		return SPHX_OK;
 	}
 	const uint32_t grid = ctx->tile_grid*TL_GRIDMUL < ctx->tile_capacity ? ctx->tile_grid*TL_GRIDMUL : ctx->tile_capacity;
@@ -2507,6 +2507,22 @@ int sphx_tile_lists_launch(sphx_ctx *ctx, const uint16_t *neibsList, const void 
 	SPHX_LAUNCH_CHECK("tile_lists_kernel");
 	return SPHX_OK;
 }
+
+// the tables of the tiling, for a launch of the tiled kernel
+static void set_tile_tables(ForcesArgs &a, const sphx_ctx *ctx)
+{
+	a.tileList = ctx->tile_list; a.tileRuns = ctx->tile_runs; a.tileRows = ctx->tile_rows;
+	a.tileLaneRec = ctx->tile_lane_rec; a.tileLaneIndex = ctx->tile_lane_index;
+}
+
+// the launchers of each SPH kernel type's translation unit: forces_parts[kerneltype - 1] (set_constants admits 1..4 only)
+static const struct ForcesPart {
+	decltype(&sphx_part_forces_k1) forces; decltype(&sphx_part_stress_k1) stress; decltype(&sphx_part_sps_k1) sps;      // SPHX_PART_DECL
+} forces_parts[4] = {
+#define SPHX_PART(K) { sphx_part_forces_k##K, sphx_part_stress_k##K, sphx_part_sps_k##K }
+	SPHX_PART(1), SPHX_PART(2), SPHX_PART(3), SPHX_PART(4)
+#undef SPHX_PART
+};
 
 extern "C" int sphx_forces_basicstep(sphx_ctx *ctx,
 	void *forces, float *cfl, void *rbforces, void *rbtorques,
@@ -2580,8 +2596,7 @@ extern "C" int sphx_forces_basicstep(sphx_ctx *ctx,
 	a.tau0 = (const float2*)tau0; a.tau1 = (const float2*)tau1; a.tau2 = (const float2*)tau2;
 	a.rb = ctx->rb_dev;
 	a.aux = ctx->eos_aux;
-	a.tileList = ctx->tile_list; a.tileRuns = ctx->tile_runs; a.tileRows = ctx->tile_rows;
-	a.tileLaneRec = ctx->tile_lane_rec; a.tileLaneIndex = ctx->tile_lane_index;
+	set_tile_tables(a, ctx);
 	a.xsph = (float4*)xsph;
 	a.fromParticle = fromParticle; a.toParticle = toParticle; a.cflOffset = cflOffset;
 	a.wholeRange = (fromParticle == 0u && toParticle == numParticles) ? 1 : 0;
@@ -2597,11 +2612,7 @@ extern "C" int sphx_forces_basicstep(sphx_ctx *ctx,
 	}
 #endif
 
-	sphx_tiles_overflow_poll(ctx);
-	// the tiling belongs to the neighbour list built last by this context from these very buffers
-	const bool use_tiles = ctx->tiles_built && ctx->tiles_overflow != 1 && ctx->tiles_cellstart == cellStart && ctx->tiles_neibslist == neibsList &&
-		((ctx->dev.numfluids == 1 && ctx->dev.densitydiff != SPHX_FERRARI) || ctx->dev.kerneltype == SPHX_WENDLAND) &&
-		ctx->dev.formulation == SPHX_SPH_F1 && !ctx->disable_tiles && ctx->tile_list != nullptr;
+	const bool use_tiles = sphx_tiles_current(ctx, cellStart, neibsList) && sphx_tiles_opts_forces(ctx->dev);
 	a.tauPack = nullptr; a.tauPackN = 0;
 	a.otau0 = a.otau1 = a.otau2 = nullptr; a.oturbvisc = nullptr;
 	if (use_tiles && ctx->dev.turbmodel == SPHX_SPS) {   // window rows of the stress tensor (see tau_pack_kernel)
@@ -2611,14 +2622,9 @@ extern "C" int sphx_forces_basicstep(sphx_ctx *ctx,
 		SPHX_LAUNCH_CHECK("tau_pack_kernel");
 		a.tauPack = ctx->tau_pack; a.tauPackN = numParticles;
 	}
-	int rc;
-	switch (ctx->dev.kerneltype) {
-	case SPHX_CUBICSPLINE: rc = sphx_part_forces_k1(ctx, dim3(numBlocks), (hipStream_t)stream, a, use_tiles); break;
-	case SPHX_QUADRATIC:   rc = sphx_part_forces_k2(ctx, dim3(numBlocks), (hipStream_t)stream, a, use_tiles); break;
-	case SPHX_WENDLAND:    rc = sphx_part_forces_k3(ctx, dim3(numBlocks), (hipStream_t)stream, a, use_tiles); break;
-	case SPHX_GAUSSIAN:    rc = sphx_part_forces_k4(ctx, dim3(numBlocks), (hipStream_t)stream, a, use_tiles); break;
-	default: return sphx_set_error(SPHX_ERR_INVALID, "sphx_forces_basicstep: invalid kernel type");
-	}
+	if (ctx->dev.kerneltype < SPHX_CUBICSPLINE || ctx->dev.kerneltype > SPHX_GAUSSIAN)
+		return sphx_set_error(SPHX_ERR_INVALID, "sphx_forces_basicstep: invalid kernel type");
+	const int rc = forces_parts[ctx->dev.kerneltype - 1].forces(ctx, dim3(numBlocks), (hipStream_t)stream, a, use_tiles);
 	if (rc != SPHX_OK) return rc;
 	SPHX_LAUNCH_CHECK("forces_kernel");
 	if (ctx->dev.simflags & SPHX_ENABLE_XSPH)   // mean neighbourhood velocity of the fluid particles (filters.hip)
@@ -2645,14 +2651,9 @@ int sphx_sa_tiles_run(sphx_ctx *ctx, int mode, void *forces, const void *pos, co
 	bool *used, const uint32_t **guard)
 {
 	*used = false; *guard = nullptr;
-	sphx_tiles_overflow_poll(ctx);
 	const DevParams &d = ctx->dev;
-	const bool ok = ctx->tiles_built && ctx->tiles_overflow != 1 && ctx->tiles_cellstart == cellStart && ctx->tiles_neibslist == neibsList &&
-		!ctx->disable_tiles && ctx->tile_list != nullptr && d.boundarytype == SPHX_SA_BOUNDARY && d.kerneltype == SPHX_WENDLAND &&
-		d.numfluids == 1 && (d.turbmodel == SPHX_LAMINAR_FLOW || (d.turbmodel == SPHX_KEPSILON && mode != SPHX_SA_TILE_FORCES)) &&
-		d.formulation == SPHX_SPH_F1 && d.rheology <= SPHX_NEWTONIAN &&
-		numParticles <= ctx->reserved_particles;
-	if (!ok || fromParticle >= toParticle) return SPHX_OK;
+	if (!sphx_tiles_current(ctx, cellStart, neibsList) || !sphx_tiles_opts_sa(d, mode) || numParticles > ctx->reserved_particles ||
+		fromParticle >= toParticle) return SPHX_OK;
 	ForcesArgs a = {};
 	a.forces = (float4*)forces;
 	a.pos = (const float4*)pos; a.vel = (const float4*)vel; a.info = (const particleinfo*)info;
@@ -2667,8 +2668,7 @@ int sphx_sa_tiles_run(sphx_ctx *ctx, int mode, void *forces, const void *pos, co
 		eos_kernel<<<div_up_u(numParticles, 256), 256, 0, stream>>>(ctx->dev, (const float4*)vel, (const particleinfo*)info, ctx->eos_aux, numParticles);
 		SPHX_LAUNCH_CHECK("eos_kernel");
 	}
-	a.tileList = ctx->tile_list; a.tileRuns = ctx->tile_runs; a.tileRows = ctx->tile_rows;
-	a.tileLaneRec = ctx->tile_lane_rec; a.tileLaneIndex = ctx->tile_lane_index;
+	set_tile_tables(a, ctx);
 	a.saGam = (const float4*)gGam; a.saDt = dt;
 	a.rb = ctx->rb_dev;
 	a.fromParticle = fromParticle; a.toParticle = toParticle;
@@ -2676,7 +2676,7 @@ int sphx_sa_tiles_run(sphx_ctx *ctx, int mode, void *forces, const void *pos, co
 	sphx_part_sa_tile(ctx, stream, a, mode, d.rheology == SPHX_NEWTONIAN);
 	SPHX_LAUNCH_CHECK("forces_tile_kernel (SA_BOUNDARY)");
 	*used = true;
-	*guard = ctx->tiles_overflow == 0 ? nullptr : ctx->tile_ctl + 1;     // NULL: the host has seen the tiling succeed
+	*guard = sphx_tiles_standby_guard(ctx);
 	return SPHX_OK;
 }
 
@@ -2776,36 +2776,23 @@ extern "C" int sphx_calc_visc(sphx_ctx *ctx, void *tau0, void *tau1, void *tau2,
 	a.pos = (const float4*)pos; a.vel = (const float4*)vel; a.info = (const particleinfo*)info;
 	a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList; a.numParticles = particleRangeEnd;
 	dim3 grid(div_up_u(particleRangeEnd, 128));
-	sphx_tiles_overflow_poll(ctx);
+	const ForcesPart &part = forces_parts[ctx->dev.kerneltype - 1];
 	// single fluid with the tiling of this neighbour list at hand: the stress mode of the tiled kernel (neighbour rows from
 	// the LDS window instead of gathers), then the gather kernel as a stand-by guarded by the tiling's overflow flag
-	const bool use_tiles = ctx->tiles_built && ctx->tiles_overflow != 1 && ctx->tiles_cellstart == cellStart && ctx->tiles_neibslist == neibsList &&
-		ctx->dev.numfluids == 1 && !ctx->disable_tiles && ctx->tile_list != nullptr;
 	const uint32_t *guard = nullptr;
-	if (use_tiles) {
+	if (sphx_tiles_current(ctx, cellStart, neibsList) && sphx_tiles_opts_stress(ctx->dev)) {
 		ForcesArgs fa = ForcesArgs();
 		fa.pos = a.pos; fa.vel = a.vel; fa.info = a.info; fa.hash = hash; fa.cellStart = cellStart; fa.neibsList = neibsList;
 		fa.otau0 = a.tau0; fa.otau1 = a.tau1; fa.otau2 = a.tau2; fa.oturbvisc = spsturbvisc;
 		fa.fromParticle = 0; fa.toParticle = particleRangeEnd;
-		fa.tileList = ctx->tile_list; fa.tileRuns = ctx->tile_runs; fa.tileRows = ctx->tile_rows;
-		fa.tileLaneRec = ctx->tile_lane_rec; fa.tileLaneIndex = ctx->tile_lane_index;
-		switch (ctx->dev.kerneltype) {
-		case SPHX_CUBICSPLINE: sphx_part_stress_k1(ctx, (hipStream_t)stream, fa); break;
-		case SPHX_QUADRATIC:   sphx_part_stress_k2(ctx, (hipStream_t)stream, fa); break;
-		case SPHX_WENDLAND:    sphx_part_stress_k3(ctx, (hipStream_t)stream, fa); break;
-		default:               sphx_part_stress_k4(ctx, (hipStream_t)stream, fa); break;
-		}
+		set_tile_tables(fa, ctx);
+		part.stress(ctx, (hipStream_t)stream, fa);
 		SPHX_LAUNCH_CHECK("forces_tile_kernel (SPS stress)");
-		guard = ctx->tile_ctl + 1;
+		guard = sphx_tiles_standby_guard(ctx);
+		if (!guard) return SPHX_OK;
 		grid.x = grid.x < 2048u ? grid.x : 2048u;   // stand-by launch: every block returns at once unless the tiling overflowed
-		if (ctx->tiles_overflow == 0) return SPHX_OK;   // the host saw the tiling succeed: no stand-by
 	}
-	switch (ctx->dev.kerneltype) {
-	case SPHX_CUBICSPLINE: sphx_part_sps_k1(ctx, grid, (hipStream_t)stream, a, guard); break;
-	case SPHX_QUADRATIC:   sphx_part_sps_k2(ctx, grid, (hipStream_t)stream, a, guard); break;
-	case SPHX_WENDLAND:    sphx_part_sps_k3(ctx, grid, (hipStream_t)stream, a, guard); break;
-	default:               sphx_part_sps_k4(ctx, grid, (hipStream_t)stream, a, guard); break;
-	}
+	part.sps(ctx, grid, (hipStream_t)stream, a, guard);
 	SPHX_LAUNCH_CHECK("sps_kernel");
 	return SPHX_OK;
 }

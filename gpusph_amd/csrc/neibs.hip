@@ -730,6 +730,208 @@ sa_type_list_kernel(const particleinfo *__restrict__ info, uint32_t n, uint32_t 
 	wave_append_takers(n, rows, [&](uint32_t i) { return PART_TYPE(info[i]) == ptype; });
 }
 
+// ---- sphx_build_neibs_sa, step by step ----------------------------------------------------------------------------------------
+struct NeibsBuild {   // the arguments of a build, for its steps
+	uint16_t *neibsList; void *vertPos0, *vertPos1, *vertPos2;
+	const void *pos, *info, *vertices, *boundElements; const uint32_t *hash, *cellStart, *cellEnd;
+	uint32_t numParticles, particleRangeEnd, gridCells; float sqinfluenceradius, boundNlSqInflRad;
+	hipStream_t st; bool sa;
+};
+
+// The tiling of a build runs beside its list build on the context's side stream.  The rule: whatever exit the build takes once the
+// tiling has been forked there, the caller's stream waits for the side stream -- a retry or the next build would otherwise race
+// with kernels still writing the tiles -- and a tiling whose build left early is not used.  (The build that runs to its end joins
+// by itself, behind the list build, and disarms this.)
+struct SideJoin {
+	sphx_ctx *ctx; hipStream_t st; bool armed;
+	~SideJoin() {
+		if (!armed) return;
+		(void)hipEventRecord(ctx->side_join, ctx->side_stream);
+		(void)hipStreamWaitEvent(st, ctx->side_join, 0);
+		(void)hipGetLastError();
+		sphx_tiles_invalidate(ctx);
+	}
+};
+
+// the context's side stream with its fork and join events, created on first use; NULL: there is none (SPHX_TILING_INLINE, or
+// the creation failed), the same launches go to the caller's stream
+static hipStream_t sphx_side_stream(sphx_ctx *ctx)
+{
+	if (ctx->side_stream || ctx->tiling_inline) return ctx->side_stream;
+	int prLeast = 0, prGreatest = 0;
+	if (ctx->side_priority) (void)hipDeviceGetStreamPriorityRange(&prLeast, &prGreatest);
+	if ((ctx->side_priority ? hipStreamCreateWithPriority(&ctx->side_stream, hipStreamNonBlocking, prGreatest)
+	                        : hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking)) != hipSuccess) { (void)hipGetLastError(); ctx->side_stream = nullptr; }
+	else if (hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming) != hipSuccess ||
+	         hipEventCreateWithFlags(&ctx->side_join, hipEventDisableTiming) != hipSuccess) {
+		(void)hipGetLastError(); (void)hipStreamDestroy(ctx->side_stream); ctx->side_stream = nullptr;
+	}
+	return ctx->side_stream;
+}
+
+// does this build tile the sorted particles for the forces engine (forces.hip "Tiled path")?  The options (sphx_tiles_opts_build),
+// the switch, and a grid whose columns fit the tile_cols allocation (degenerate 1-D grids: generic kernels)
+static bool tiling_wanted(const sphx_ctx *ctx)
+{
+	return sphx_tiles_opts_build(ctx) && ctx->tiles && !ctx->disable_tiles &&
+		(size_t)((ctx->dev.gs[ctx->dev.c2] + 1)/2)*(size_t)((ctx->dev.gs[ctx->dev.c3] + 1)/2)*(size_t)ctx->dev.gs1 <= (size_t)ctx->cells_reserved/2 + 1024;
+}
+
+// The tiling reads the cell tables only and is needed by the tile lists, not by the list build: it runs beside
+// build_neibs_kernel on the context's side stream (build_tiles_kernel is a serial walk per row bundle, ~400 waves for
+// ~1 ms at 32 M particles, on a GPU that holds 8000).  Fork behind everything the caller has queued (arms `join`); the join is
+// recorded here and waited for before the tile lists.  The tiling is these buffers' from here on
+static int tiling_launch(sphx_ctx *ctx, const NeibsBuild &b, SideJoin &join)
+{
+	hipStream_t ts = b.st;
+	if (sphx_side_stream(ctx)) {
+		SPHX_HIP(hipEventRecord(ctx->side_fork, b.st));
+		SPHX_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->side_fork, 0));
+		ts = ctx->side_stream; join.armed = true;
+	}
+	SPHX_HIP(hipMemcpyAsync(ctx->cell_end_copy, b.cellEnd, sizeof(uint32_t)*(size_t)b.gridCells, hipMemcpyDeviceToDevice, ts));
+	SPHX_HIP(hipMemsetAsync(ctx->tile_ctl, 0, 2*sizeof(uint32_t), ts));
+	SPHX_HIP(hipMemsetAsync(ctx->tile_ctl + 12, 0, 2*sizeof(uint32_t), ts));      // cursors of the list stream and of the lane tables
+	const DevParams &dp = ctx->dev;
+	const uint32_t gs2 = (uint32_t)dp.gs[dp.c2], gs3 = (uint32_t)dp.gs[dp.c3];
+	const uint32_t bundles = ((gs2 + 1)/2)*((gs3 + 1)/2);
+	tile_columns_kernel<<<div_up_u(bundles*(uint32_t)dp.gs1, 256), 256, 0, ts>>>(ctx->dev, b.cellStart, ctx->cell_end_copy,
+		(const particleinfo*)b.info, ctx->tile_cols);
+	SPHX_LAUNCH_CHECK("tile_columns_kernel");
+	const uint32_t tileThreads = ((gs2 + 1)/2 + 7)/8*(((gs3 + 1)/2 + 3)/4)*32u;   // 8 x 4 blocks of bundles, see the kernel
+	build_tiles_kernel<<<div_up_u(tileThreads, 128), 128, 0, ts>>>(ctx->dev, b.cellStart, ctx->cell_end_copy,
+		ctx->tile_cols, b.particleRangeEnd, ctx->tiles, ctx->tile_ctl, ctx->tile_capacity);
+	SPHX_LAUNCH_CHECK("build_tiles_kernel");
+	if (join.armed) SPHX_HIP(hipEventRecord(ctx->side_join, ctx->side_stream));
+	ctx->tiles_built = true;
+	ctx->tiles_cellstart = b.cellStart;
+	ctx->tiles_neibslist = b.neibsList;
+	return SPHX_OK;
+}
+
+// The list build.  In one launch, or, of a build whose tiling is on the side stream, in parts: tile_lists_kernel is a chain of
+// dependent round trips per tile at ten waves per CU (forces.hip): it needs little of the vector units and leaves most of the CU
+// idle; build_neibs_kernel is bound by vector issue.  So the list is built in `list_parts` launches over consecutive particle
+// ranges, and the tile lists of the tiles whose home particles are all listed go to the side stream behind each of them: they
+// run beside the list build of the next part, and only the last part's tile lists are left over at the end.  Lists, counters and
+// tile lists are what one launch each gives (the tiles get their room in the list stream in another order, which nothing reads).
+// *inParts: the tile lists have been launched here (and the side stream's join is recorded behind them)
+static int list_build(sphx_ctx *ctx, const NeibsBuild &b, bool tiling_on_side, bool *inParts)
+{
+	const auto launch = [&](uint32_t from, uint32_t to) {      // neibs_build.hip
+		return sphx_neibs_list_launch_part(ctx, b.neibsList, b.pos, b.info, b.hash, b.cellStart, b.cellEnd, b.vertices, b.boundElements,
+			b.vertPos0, b.vertPos1, b.vertPos2, b.numParticles, from, to, b.sqinfluenceradius, b.boundNlSqInflRad, b.st); };
+	int parts = 1;
+	if (tiling_on_side && ctx->list_parts > 1 && b.particleRangeEnd >= 65536u*(uint32_t)ctx->list_parts) {
+		if (!ctx->list_part_events) {
+			int made = 0;
+			for (; made < SPHX_LIST_PARTS_MAX; ++made)
+				if (hipEventCreateWithFlags(&ctx->list_part[made], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); break; }
+			if (made == SPHX_LIST_PARTS_MAX) ctx->list_part_events = true;
+			else for (int k = 0; k < made; ++k) (void)hipEventDestroy(ctx->list_part[k]);
+		}
+		if (ctx->list_part_events) parts = ctx->list_parts;
+	}
+	*inParts = parts > 1;
+	if (parts == 1) return launch(0u, b.particleRangeEnd);
+	const uint32_t per = div_up_u(div_up_u(b.particleRangeEnd, (uint32_t)parts), 1024u)*1024u;      // whole workgroups of the list build
+	for (int k = 0; k < parts; ++k) {
+		const uint32_t from = (uint32_t)k*per, to = (k == parts - 1) ? b.particleRangeEnd : min(b.particleRangeEnd, from + per);
+		if (from >= b.particleRangeEnd) break;
+		int rc = launch(from, to);
+		if (rc != SPHX_OK) return rc;
+		SPHX_HIP(hipEventRecord(ctx->list_part[k], b.st));
+		SPHX_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->list_part[k], 0));
+		rc = sphx_tile_lists_launch(ctx, b.neibsList, b.info, b.hash, b.cellStart, b.sa, ctx->side_stream, from, (k == parts - 1) ? 0xFFFFFFFFu : to);
+		if (rc != SPHX_OK) return rc;
+	}
+	SPHX_HIP(hipEventRecord(ctx->side_join, ctx->side_stream));
+	return SPHX_OK;
+}
+
+// room for a list of particles ([0] = how many, [1..] = which), allocated on first use.  When the memory is not there the list stays
+// NULL and its engine falls back to one thread per particle / row: not an error of the caller's command
+static uint32_t *particle_list_room(sphx_ctx *ctx, uint32_t *&list)
+{
+	if (!list && hipMalloc((void**)&list, sizeof(uint32_t)*((size_t)ctx->reserved_particles + 1)) != hipSuccess) {
+		(void)hipGetLastError();
+		list = nullptr;
+	}
+	return list;
+}
+
+// |grad gamma_as| per (wall particle, list entry), allocated on first use: room for a quarter of the particles next to a wall; the
+// rest recompute.  Without the memory: no cache
+static int sa_wall_cache_room(sphx_ctx *ctx, hipStream_t st)
+{
+	if (ctx->sa_wall_cache) return SPHX_OK;
+	const size_t cap = (size_t)ctx->reserved_particles/4u + 1024u;
+	if (hipMalloc((void**)&ctx->sa_wall_cache, sizeof(float)*SA_WALL_CACHE_ENTRIES*cap) == hipSuccess &&
+	    hipMalloc((void**)&ctx->sa_wall_tag, sizeof(float4)*cap) == hipSuccess) {
+		ctx->sa_wall_capacity = (uint32_t)cap;
+		SPHX_HIP(hipMemsetAsync(ctx->sa_wall_tag, 0, sizeof(float4)*cap, st));
+	} else {
+		(void)hipGetLastError();
+		if (ctx->sa_wall_cache) (void)hipFree(ctx->sa_wall_cache);
+		ctx->sa_wall_cache = nullptr; ctx->sa_wall_tag = nullptr; ctx->sa_wall_capacity = 0;
+	}
+	return SPHX_OK;
+}
+
+// SA_BOUNDARY: the row lists of the wall kernels and of the boundary-condition passes (sa_bounds.hip, sa_wall.hip), of this list
+static int sa_row_lists(sphx_ctx *ctx, const NeibsBuild &b)
+{
+	if (!b.sa) return SPHX_OK;
+	const uint32_t n = b.particleRangeEnd;
+	const particleinfo *info = (const particleinfo*)b.info;
+	particle_list_room(ctx, ctx->sa_wall);      // the fluid particles with boundary elements in reach
+	ctx->sa_wall_neibslist = nullptr;
+	++ctx->sa_wall_gen;      // what was kept of |grad gamma_as| per list entry belongs to the previous list
+	if (!ctx->sa_wall_gen) ctx->sa_wall_gen = 1u;
+	if (!ctx->sa_wall) return SPHX_OK;
+	const int rc = sa_wall_cache_room(ctx, b.st);
+	if (rc != SPHX_OK) return rc;
+	SPHX_HIP(hipMemsetAsync(ctx->sa_wall, 0, sizeof(uint32_t), b.st));
+	sa_wall_list_kernel<<<list_sweep_grid(n), 256, 0, b.st>>>(b.neibsList, info, (const float4*)b.pos,
+		n, ctx->dev.stride, ctx->dev.neibboundpos, ctx->sa_wall, (uint32_t)PT_FLUID);
+	SPHX_LAUNCH_CHECK("sa_wall_list_kernel");
+	// moving bodies: the vertex rows, their gamma is integrated by the density summation
+	if ((ctx->params.simflags & SPHX_ENABLE_MOVING_BODIES) && particle_list_room(ctx, ctx->sa_wall_vert)) {
+		SPHX_HIP(hipMemsetAsync(ctx->sa_wall_vert, 0, sizeof(uint32_t), b.st));
+		sa_wall_list_kernel<<<list_sweep_grid(n), 256, 0, b.st>>>(b.neibsList, info, (const float4*)b.pos,
+			n, ctx->dev.stride, ctx->dev.neibboundpos, ctx->sa_wall_vert, (uint32_t)PT_VERTEX);
+		SPHX_LAUNCH_CHECK("sa_wall_list_kernel<vertices>");
+	}
+	// the rows of the two boundary-condition passes: every boundary element, every vertex particle
+	ctx->sa_rows_range = 0;
+	for (int k = 0; k < 2; ++k) {
+		uint32_t *rows = particle_list_room(ctx, k ? ctx->sa_rows_vert : ctx->sa_rows_bound);
+		if (!rows) continue;
+		SPHX_HIP(hipMemsetAsync(rows, 0, sizeof(uint32_t), b.st));
+		sa_type_list_kernel<<<list_sweep_grid(n), 256, 0, b.st>>>(info, n, rows, k ? (uint32_t)PT_VERTEX : (uint32_t)PT_BOUNDARY);
+		SPHX_LAUNCH_CHECK("sa_type_list_kernel");
+	}
+	if (ctx->sa_rows_bound && ctx->sa_rows_vert) ctx->sa_rows_range = n;
+	ctx->sa_wall_neibslist = b.neibsList;
+	return SPHX_OK;
+}
+
+// the lists of the tiled particles in the form the tiled forces kernel walks (forces.hip), unless the build in parts has made
+// them.  Then the tiling's overflow flag travels to the host behind the build, without a synchronisation: the forces passes
+// that find it arrived (sphx_tiles_current) launch exactly one kernel, the others keep the guarded stand-by
+static int tile_lists_and_overflow_copy(sphx_ctx *ctx, const NeibsBuild &b, bool listsMade)
+{
+	if (!listsMade) {
+		const int rc = sphx_tile_lists_launch(ctx, b.neibsList, b.info, b.hash, b.cellStart, b.sa, b.st);
+		if (rc != SPHX_OK) return rc;
+	}
+	if (!ctx->tiles_built || !ctx->ovf_host) return SPHX_OK;      // (no room for the tile lists: no tiling after all)
+	SPHX_HIP(hipMemcpyAsync(ctx->ovf_host, ctx->tile_ctl, 2*sizeof(uint32_t), hipMemcpyDeviceToHost, b.st));
+	SPHX_HIP(hipEventRecord(ctx->ovf_event, b.st));
+	ctx->ovf_pending = true;
+	return SPHX_OK;
+}
+
 extern "C" int sphx_build_neibs_sa(sphx_ctx *ctx, uint16_t *neibsList, void *vertPos0, void *vertPos1, void *vertPos2,
 	const void *pos, const void *info, const void *vertices, const void *boundElements, const uint32_t *hash,
 	const uint32_t *cellStart, const uint32_t *cellEnd,
@@ -749,192 +951,32 @@ extern "C" int sphx_build_neibs_sa(sphx_ctx *ctx, uint16_t *neibsList, void *ver
 	int rc = sphx_ensure_scratch(ctx, numParticles);
 	if (rc != SPHX_OK) return rc;
 	SPHX_REQUIRE(gridCells <= ctx->cells_reserved, "sphx_build_neibs: grid larger than reserved");
+	const NeibsBuild b = { neibsList, vertPos0, vertPos1, vertPos2, pos, info, vertices, boundElements, hash, cellStart, cellEnd,
+		numParticles, particleRangeEnd, gridCells, sqinfluenceradius, boundNlSqInflRad, st, sa };
 	// per-cell end of the fluid segment (particles of a cell are sorted fluid-first)
 	SPHX_HIP(hipMemcpyAsync(ctx->cell_fluid_end, cellStart, sizeof(uint32_t)*(size_t)gridCells, hipMemcpyDeviceToDevice, st));
 	cell_fluid_end_kernel<<<div_up_u(numParticles, 256), 256, 0, st>>>(ctx->cell_fluid_end, hash, (const particleinfo*)info, numParticles);
 	SPHX_LAUNCH_CHECK("cell_fluid_end_kernel");
-	// tiling of the sorted particles for the forces engine (forces.hip "Tiled path")
-	ctx->tiles_built = false;
-	ctx->tiles_overflow = -1;
-	const bool tile_cols_fit = (size_t)((ctx->dev.gs[ctx->dev.c2] + 1)/2)*(size_t)((ctx->dev.gs[ctx->dev.c3] + 1)/2)*(size_t)ctx->dev.gs1
-		<= (size_t)ctx->cells_reserved/2 + 1024;   // tile_cols allocation (degenerate 1-D grids: generic kernels)
-	// tiles serve sphx_forces_basicstep's pair loop only (SPH_F1, inviscid or Newtonian, DYN / LJ / MK boundaries) and sphx_calc_visc
-	// ... and, with SA_BOUNDARY, the particle <- particle sums of the SA forces, density summation and density diffusion
-	// (one fluid; with k-epsilon the density summation and the diffusion, which do not involve the model: sphx_sa_tiles_run, forces.hip)
-	// (a run with open boundaries rebuilds the list in every step; the fluid <- fluid sums of its passes are the solid-wall ones and go
-	// through the tiles since round 6: the tile lists of a rebuild cost a tenth of what its list walkers did per step)
-	const bool tiled_options = ctx->params.sph_formulation == SPHX_SPH_F1 && ctx->params.rheologytype <= SPHX_NEWTONIAN &&
-		(!sa || (ctx->dev.numfluids == 1 && (ctx->dev.turbmodel == SPHX_LAMINAR_FLOW || ctx->dev.turbmodel == SPHX_KEPSILON)));
-	if (tiled_options && ctx->tiles && !ctx->disable_tiles && tile_cols_fit) {
+	// the tiling of the previous list is gone; that of this one, on the side stream where there is one
+	sphx_tiles_invalidate(ctx);
+	SideJoin sideJoin = { ctx, st, false };
+	if (tiling_wanted(ctx)) {
 		rc = sphx_ensure_tile_lists(ctx);      // first tiled build: the tile lists are allocated now (or never: generic kernels)
+		if (rc == SPHX_OK && ctx->tile_list) rc = tiling_launch(ctx, b, sideJoin);
 		if (rc != SPHX_OK) return rc;
 	}
-	bool tiling_on_side = false;
-	// whatever exit this function takes once the tiling has been forked to the side stream, the caller's stream waits for it:
-	// a retry or the next build would otherwise race with kernels still writing the tiles (and such a tiling is not used)
-	struct SideJoin {
-		sphx_ctx *ctx; hipStream_t st; bool armed;
-		~SideJoin() {
-			if (!armed) return;
-			(void)hipEventRecord(ctx->side_join, ctx->side_stream);
-			(void)hipStreamWaitEvent(st, ctx->side_join, 0);
-			(void)hipGetLastError();
-			ctx->tiles_built = false;
-		}
-	} sideJoin = { ctx, st, false };
-	if (tiled_options && ctx->tiles && !ctx->disable_tiles && tile_cols_fit && ctx->tile_list) {
-		// The tiling reads the cell tables only and is needed by the tile lists, not by the list build: it runs beside
-		// build_neibs_kernel on the context's side stream (build_tiles_kernel is a serial walk per row bundle, ~400 waves for
-		// ~1 ms at 32 M particles, on a GPU that holds 8000).  Fork behind everything the caller has queued, join before the
-		// tile lists.  Without the side stream (creation failed) the same launches go to the caller's stream
-		static const bool noSide = getenv("SPHX_TILING_INLINE") != nullptr;      // A/B switch: the tiling on the caller's stream
-		if (!ctx->side_stream && !noSide) {
-			// SPHX_SIDE_PRIORITY=1 (experiment of round 6): the side stream at the highest priority, so that the dispatcher prefers
-			// its workgroups whenever room comes free on a CU
-			static const bool sidePrio = getenv("SPHX_SIDE_PRIORITY") != nullptr;
-			int prLeast = 0, prGreatest = 0;
-			if (sidePrio) (void)hipDeviceGetStreamPriorityRange(&prLeast, &prGreatest);
-			if ((sidePrio ? hipStreamCreateWithPriority(&ctx->side_stream, hipStreamNonBlocking, prGreatest)
-			              : hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking)) != hipSuccess) { (void)hipGetLastError(); ctx->side_stream = nullptr; }
-			else if (hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming) != hipSuccess ||
-			         hipEventCreateWithFlags(&ctx->side_join, hipEventDisableTiming) != hipSuccess) {
-				(void)hipGetLastError(); (void)hipStreamDestroy(ctx->side_stream); ctx->side_stream = nullptr;
-			}
-		}
-		hipStream_t ts = st;
-		if (ctx->side_stream) {
-			SPHX_HIP(hipEventRecord(ctx->side_fork, st));
-			SPHX_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->side_fork, 0));
-			ts = ctx->side_stream; tiling_on_side = true; sideJoin.armed = true;
-		}
-		SPHX_HIP(hipMemcpyAsync(ctx->cell_end_copy, cellEnd, sizeof(uint32_t)*(size_t)gridCells, hipMemcpyDeviceToDevice, ts));
-		SPHX_HIP(hipMemsetAsync(ctx->tile_ctl, 0, 2*sizeof(uint32_t), ts));
-		SPHX_HIP(hipMemsetAsync(ctx->tile_ctl + 12, 0, 2*sizeof(uint32_t), ts));      // cursors of the list stream and of the lane tables
-		const DevParams &dp = ctx->dev;
-		const uint32_t gs2 = (uint32_t)dp.gs[dp.c2], gs3 = (uint32_t)dp.gs[dp.c3];
-		const uint32_t bundles = ((gs2 + 1)/2)*((gs3 + 1)/2);
-		tile_columns_kernel<<<div_up_u(bundles*(uint32_t)dp.gs1, 256), 256, 0, ts>>>(ctx->dev, cellStart, ctx->cell_end_copy,
-			(const particleinfo*)info, ctx->tile_cols);
-		SPHX_LAUNCH_CHECK("tile_columns_kernel");
-		const uint32_t tileThreads = ((gs2 + 1)/2 + 7)/8*(((gs3 + 1)/2 + 3)/4)*32u;   // 8 x 4 blocks of bundles, see the kernel
-		build_tiles_kernel<<<div_up_u(tileThreads, 128), 128, 0, ts>>>(ctx->dev, cellStart, ctx->cell_end_copy,
-			ctx->tile_cols, particleRangeEnd, ctx->tiles, ctx->tile_ctl, ctx->tile_capacity);
-		SPHX_LAUNCH_CHECK("build_tiles_kernel");
-		if (tiling_on_side) SPHX_HIP(hipEventRecord(ctx->side_join, ctx->side_stream));
-		ctx->tiles_built = true;
-		ctx->tiles_cellstart = cellStart;
-		ctx->tiles_neibslist = neibsList;
-	}
-	// A tiled build in parts.  tile_lists_kernel is a chain of dependent round trips per tile at ten waves per CU (forces.hip): it
-	// needs little of the vector units and leaves most of the CU idle; build_neibs_kernel is bound by vector issue.  So the list is
-	// built in `list_parts` launches over consecutive particle ranges, and the tile lists of the tiles whose home particles are
-	// all listed go to the side stream behind each of them: they run beside the list build of the next part, and only the last
-	// part's tile lists are left over at the end.  Lists, counters and tile lists are what one launch each gives (the tiles get
-	// their room in the list stream in another order, which nothing reads).
-	int parts = 1;
-	if (ctx->tiles_built && tiling_on_side && ctx->list_parts > 1 && particleRangeEnd >= 65536u*(uint32_t)ctx->list_parts) {
-		if (!ctx->list_part_events) {
-			int made = 0;
-			for (; made < SPHX_LIST_PARTS_MAX; ++made)
-				if (hipEventCreateWithFlags(&ctx->list_part[made], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); break; }
-			if (made == SPHX_LIST_PARTS_MAX) ctx->list_part_events = true;
-			else for (int k = 0; k < made; ++k) (void)hipEventDestroy(ctx->list_part[k]);
-		}
-		if (ctx->list_part_events) parts = ctx->list_parts;
-	}
-	if (parts > 1) {
-		const uint32_t per = div_up_u(div_up_u(particleRangeEnd, (uint32_t)parts), 1024u)*1024u;      // whole workgroups of the list build
-		for (int k = 0; k < parts; ++k) {
-			const uint32_t from = (uint32_t)k*per, to = (k == parts - 1) ? particleRangeEnd : min(particleRangeEnd, from + per);
-			if (from >= particleRangeEnd) break;
-			rc = sphx_neibs_list_launch_part(ctx, neibsList, pos, info, hash, cellStart, cellEnd, vertices, boundElements, vertPos0, vertPos1, vertPos2,
-				numParticles, from, to, sqinfluenceradius, boundNlSqInflRad, st);      // neibs_build.hip
-			if (rc != SPHX_OK) return rc;
-			SPHX_HIP(hipEventRecord(ctx->list_part[k], st));
-			SPHX_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->list_part[k], 0));
-			rc = sphx_tile_lists_launch(ctx, neibsList, info, hash, cellStart, sa, ctx->side_stream, from, (k == parts - 1) ? 0xFFFFFFFFu : to);
-			if (rc != SPHX_OK) return rc;
-		}
-		SPHX_HIP(hipEventRecord(ctx->side_join, ctx->side_stream));
-	} else {
-		rc = sphx_neibs_list_launch(ctx, neibsList, pos, info, hash, cellStart, cellEnd, vertices, boundElements, vertPos0, vertPos1, vertPos2,
-			numParticles, particleRangeEnd, sqinfluenceradius, boundNlSqInflRad, st);      // neibs_build.hip
-		if (rc != SPHX_OK) return rc;
-	}
+	bool tileListsMade = false;
+	rc = list_build(ctx, b, sideJoin.armed, &tileListsMade);
+	if (rc != SPHX_OK) return rc;
 	neibs_counters_fold_kernel<<<1, NEIBS_SPREAD, 0, st>>>(ctx->counters_dev);
 	SPHX_LAUNCH_CHECK("neibs_counters_fold_kernel");
-	if (tiling_on_side) {      // the tiling (and, of a build in parts, the tile lists) is there for everything queued from here on
+	if (sideJoin.armed) {      // the tiling (and, of a build in parts, the tile lists) is there for everything queued from here on
 		SPHX_HIP(hipStreamWaitEvent(st, ctx->side_join, 0));
 		sideJoin.armed = false;
 	}
-	if (sa) {   // the fluid particles with boundary elements in reach
-		if (!ctx->sa_wall && hipMalloc((void**)&ctx->sa_wall, sizeof(uint32_t)*((size_t)ctx->reserved_particles + 1)) != hipSuccess) {
-			(void)hipGetLastError();
-			ctx->sa_wall = nullptr;      // the engines fall back to one thread per particle
-		}
-		ctx->sa_wall_neibslist = nullptr;
-		++ctx->sa_wall_gen;      // what was kept of |grad gamma_as| per list entry belongs to the previous list
-		if (!ctx->sa_wall_gen) ctx->sa_wall_gen = 1u;
-		if (ctx->sa_wall && !ctx->sa_wall_cache) {      // room for a quarter of the particles next to a wall; the rest recompute
-			const size_t cap = (size_t)ctx->reserved_particles/4u + 1024u;
-			if (hipMalloc((void**)&ctx->sa_wall_cache, sizeof(float)*SA_WALL_CACHE_ENTRIES*cap) == hipSuccess &&
-			    hipMalloc((void**)&ctx->sa_wall_tag, sizeof(float4)*cap) == hipSuccess) {
-				ctx->sa_wall_capacity = (uint32_t)cap;
-				SPHX_HIP(hipMemsetAsync(ctx->sa_wall_tag, 0, sizeof(float4)*cap, st));
-			} else {
-				(void)hipGetLastError();
-				if (ctx->sa_wall_cache) (void)hipFree(ctx->sa_wall_cache);
-				ctx->sa_wall_cache = nullptr; ctx->sa_wall_tag = nullptr; ctx->sa_wall_capacity = 0;
-			}
-		}
-		if (ctx->sa_wall) {
-			SPHX_HIP(hipMemsetAsync(ctx->sa_wall, 0, sizeof(uint32_t), st));
-			sa_wall_list_kernel<<<list_sweep_grid(particleRangeEnd), 256, 0, st>>>(neibsList, (const particleinfo*)info, (const float4*)pos,
-				particleRangeEnd, ctx->dev.stride, ctx->dev.neibboundpos, ctx->sa_wall, (uint32_t)PT_FLUID);
-			SPHX_LAUNCH_CHECK("sa_wall_list_kernel");
-			if (ctx->params.simflags & SPHX_ENABLE_MOVING_BODIES) {      // the vertex rows: their gamma is integrated by the density summation
-				if (!ctx->sa_wall_vert && hipMalloc((void**)&ctx->sa_wall_vert, sizeof(uint32_t)*((size_t)ctx->reserved_particles + 1)) != hipSuccess) {
-					(void)hipGetLastError();
-					ctx->sa_wall_vert = nullptr;      // one thread per vertex row then
-				}
-				if (ctx->sa_wall_vert) {
-					SPHX_HIP(hipMemsetAsync(ctx->sa_wall_vert, 0, sizeof(uint32_t), st));
-					sa_wall_list_kernel<<<list_sweep_grid(particleRangeEnd), 256, 0, st>>>(neibsList, (const particleinfo*)info, (const float4*)pos,
-						particleRangeEnd, ctx->dev.stride, ctx->dev.neibboundpos, ctx->sa_wall_vert, (uint32_t)PT_VERTEX);
-					SPHX_LAUNCH_CHECK("sa_wall_list_kernel<vertices>");
-				}
-			}
-			// the rows of the two boundary-condition passes: every boundary element, every vertex particle
-			ctx->sa_rows_range = 0;
-			for (int k = 0; k < 2; ++k) {
-				uint32_t *&rows = k ? ctx->sa_rows_vert : ctx->sa_rows_bound;
-				if (!rows && hipMalloc((void**)&rows, sizeof(uint32_t)*((size_t)ctx->reserved_particles + 1)) != hipSuccess) {
-					(void)hipGetLastError();
-					rows = nullptr;      // one thread per particle then
-				}
-				if (rows) {
-					SPHX_HIP(hipMemsetAsync(rows, 0, sizeof(uint32_t), st));
-					sa_type_list_kernel<<<list_sweep_grid(particleRangeEnd), 256, 0, st>>>((const particleinfo*)info, particleRangeEnd, rows,
-						k ? (uint32_t)PT_VERTEX : (uint32_t)PT_BOUNDARY);
-					SPHX_LAUNCH_CHECK("sa_type_list_kernel");
-				}
-			}
-			if (ctx->sa_rows_bound && ctx->sa_rows_vert) ctx->sa_rows_range = particleRangeEnd;
-			ctx->sa_wall_neibslist = neibsList;
-		}
-	}
-	if (ctx->tiles_built) {   // the lists of the tiled particles in the form the tiled forces kernel walks (forces.hip)
-		if (parts == 1) rc = sphx_tile_lists_launch(ctx, neibsList, info, hash, cellStart, sa, st);
-		if (rc != SPHX_OK) return rc;
-		// the tiling's overflow flag travels to the host behind the build, without a synchronisation: the forces passes that
-		// find it arrived (sphx_tiles_overflow_poll) launch exactly one kernel, the others keep the guarded stand-by
-		if (ctx->tiles_built && ctx->ovf_host) {
-			SPHX_HIP(hipMemcpyAsync(ctx->ovf_host, ctx->tile_ctl, 2*sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-			SPHX_HIP(hipEventRecord(ctx->ovf_event, st));
-			ctx->ovf_pending = true;
-		}
-	}
-	return SPHX_OK;
+	rc = sa_row_lists(ctx, b);
+	if (rc != SPHX_OK) return rc;
+	return ctx->tiles_built ? tile_lists_and_overflow_copy(ctx, b, tileListsMade) : SPHX_OK;
 }
 
 extern "C" int sphx_neibs_resetinfo(sphx_ctx *ctx, void *stream)

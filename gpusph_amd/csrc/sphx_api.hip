@@ -43,15 +43,24 @@ extern "C" int sphx_create(sphx_ctx **out, int device)
 	int cus = 0;
 	SPHX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
 	ctx->tile_grid = (uint32_t)(cus > 0 ? cus : 256)*TILE_WGS_PER_CU;   // persistent grid: one 512-thread workgroup per CU (LDS bound)
-	const char *dis = getenv("SPHX_DISABLE_TILES");
-	ctx->disable_tiles = dis && dis[0] == '1';
-	{ const char *mf = getenv("SPHX_NEIBS_MFMA"); ctx->neibs_mfma = mf && mf[0] == '1'; }
-	// a tiled list build in parts, the tile lists of a part beside the list build of the next one (sphx_build_neibs_sa); 1 = one launch each
+	// The switches of the environment, all read here: they hold for this context from its creation on.
+	//   SPHX_DISABLE_TILES=1   always the generic gather kernels, no tiling is built (A/B runs, tests)
+	//   SPHX_NEIBS_MFMA=1      the list build's prepass on the matrix cores (neibs_build.hip: bit-identical, measured slower)
+	//   SPHX_LIST_PARTS=n      a tiled list build in n parts, the tile lists of a part beside the list build of the next one
+	//                          (sphx_build_neibs_sa); 1 = one launch each
+	//   SPHX_TILING_INLINE     (set to anything) the tiling of a build on the caller's stream instead of the side stream (A/B)
+	//   SPHX_SIDE_PRIORITY     (set to anything) the side stream at the highest priority, so that the dispatcher prefers its
+	//                          workgroups whenever room comes free on a CU (experiment)
+	//   SPHX_TILE_DEBUG        (ForcesArgs::dbg: timing experiments, some of which skip work and give wrong results) only exists in
+	//                          a library built with -DSPHX_TILE_DEBUG_BUILD (make EXTRA=-DSPHX_TILE_DEBUG_BUILD); the product
+	//                          library ignores the variable
+	const auto is1 = [](const char *name) { const char *v = getenv(name); return v && v[0] == '1'; };
+	ctx->disable_tiles = is1("SPHX_DISABLE_TILES");
+	ctx->neibs_mfma = is1("SPHX_NEIBS_MFMA");
 	{ const char *lp = getenv("SPHX_LIST_PARTS"); const int n = lp ? atoi(lp) : SPHX_LIST_PARTS_DEFAULT;
 	  ctx->list_parts = n < 1 ? 1 : n > SPHX_LIST_PARTS_MAX ? SPHX_LIST_PARTS_MAX : n; }
-	// SPHX_DISABLE_TILES=1: always the generic gather kernel (A/B runs, tests).
-	// SPHX_TILE_DEBUG (ForcesArgs::dbg: timing experiments, some of which skip work and give wrong results) only exists in a
-	// library built with -DSPHX_TILE_DEBUG_BUILD (make EXTRA=-DSPHX_TILE_DEBUG_BUILD); the product library ignores the variable
+	ctx->tiling_inline = getenv("SPHX_TILING_INLINE") != nullptr;
+	ctx->side_priority = getenv("SPHX_SIDE_PRIORITY") != nullptr;
 	ctx->tile_debug = 0;
 #ifdef SPHX_TILE_DEBUG_BUILD
 	const char *dbg = getenv("SPHX_TILE_DEBUG");
@@ -64,26 +73,21 @@ extern "C" int sphx_create(sphx_ctx **out, int device)
 	return SPHX_OK;
 }
 
+// hipFree of each pointer that is set, and NULL in its place
+template<class... P> static void free_and_null(P *&... p) { ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...); }
+
 static void free_scratch(sphx_ctx *ctx)
 {
-	void *ptrs[] = { ctx->bin_count, ctx->bin_start, ctx->scan_partials, ctx->slot,
+	free_and_null(ctx->bin_count, ctx->bin_start, ctx->scan_partials, ctx->slot,
 		ctx->tmp_hash, ctx->tmp_index, ctx->tmp_info, ctx->eos_aux, ctx->tau_pack, ctx->tiles, ctx->cell_end_copy, ctx->cell_fluid_end, ctx->tile_cols,
 		ctx->tile_list, ctx->tile_runs, ctx->tile_rows, ctx->tile_lane_rec, ctx->tile_lane_index, ctx->neib_counts,
-		ctx->sa_wall, ctx->sa_wall_vert, ctx->sa_wall_cache, ctx->sa_wall_tag, ctx->sa_wall_gsum, ctx->sa_wall_open, ctx->sa_rows_bound, ctx->sa_rows_vert };
-	for (void *p : ptrs) if (p) (void)hipFree(p);
-	ctx->bin_count = ctx->bin_start = ctx->scan_partials = ctx->slot = nullptr;
-	ctx->tmp_hash = ctx->tmp_index = nullptr;
-	ctx->tmp_info = nullptr;
-	ctx->eos_aux = nullptr; ctx->tau_pack = nullptr;
+		ctx->sa_wall, ctx->sa_wall_vert, ctx->sa_wall_cache, ctx->sa_wall_tag, ctx->sa_wall_gsum, ctx->sa_wall_open, ctx->sa_rows_bound, ctx->sa_rows_vert);
+	// ... and what spoke of them
 	ctx->eos_tag_vel = nullptr; ctx->eos_tag_n = 0; ctx->eos_armed = false;
-	ctx->sa_wall = nullptr; ctx->sa_wall_vert = nullptr; ctx->sa_wall_neibslist = nullptr;
-	ctx->sa_rows_bound = nullptr; ctx->sa_rows_vert = nullptr; ctx->sa_rows_range = 0;
-	ctx->sa_wall_cache = nullptr; ctx->sa_wall_tag = nullptr; ctx->sa_wall_gsum = nullptr; ctx->sa_wall_open = nullptr; ctx->sa_wall_open_neibslist = nullptr; ctx->sa_wall_capacity = 0;
-	ctx->tile_list = nullptr; ctx->tile_runs = nullptr; ctx->tile_rows = nullptr; ctx->tile_lane_rec = nullptr; ctx->tile_lane_index = nullptr;
-	ctx->tile_list_batches = ctx->tile_lane_cap = 0; ctx->neib_counts = nullptr;
-	ctx->tiles = nullptr; ctx->cell_end_copy = nullptr; ctx->cell_fluid_end = nullptr; ctx->tile_cols = nullptr;
-	ctx->tile_capacity = 0; ctx->cells_reserved = 0; ctx->tiles_built = false;
+	ctx->sa_wall_neibslist = nullptr; ctx->sa_wall_open_neibslist = nullptr; ctx->sa_rows_range = 0; ctx->sa_wall_capacity = 0;
+	ctx->tile_list_batches = ctx->tile_lane_cap = ctx->tile_capacity = ctx->cells_reserved = 0;
 	ctx->reserved_particles = ctx->reserved_bins = 0;
+	sphx_tiles_invalidate(ctx);
 }
 
 extern "C" void sphx_destroy(sphx_ctx *ctx)
@@ -171,9 +175,7 @@ int sphx_ensure_tile_lists(sphx_ctx *ctx)
 	ok = ok && hipMalloc((void**)&ctx->tile_lane_index, sizeof(uint32_t)*lanes) == hipSuccess;
 	if (!ok) {
 		(void)hipGetLastError();   // out of memory is not an error of the caller's command: the generic kernels take over
-		void *ptrs[] = { ctx->tile_list, ctx->tile_runs, ctx->tile_rows, ctx->tile_lane_rec, ctx->tile_lane_index };
-		for (void *q : ptrs) if (q) (void)hipFree(q);
-		ctx->tile_list = nullptr; ctx->tile_runs = nullptr; ctx->tile_rows = nullptr; ctx->tile_lane_rec = nullptr; ctx->tile_lane_index = nullptr;
+		free_and_null(ctx->tile_list, ctx->tile_runs, ctx->tile_rows, ctx->tile_lane_rec, ctx->tile_lane_index);
 		ctx->tile_list_batches = ctx->tile_lane_cap = 0;
 		return SPHX_OK;
 	}

@@ -202,6 +202,8 @@ struct sphx_ctx {
 	bool        list_part_events;
 	bool        ovf_pending;
 	bool        disable_tiles; // SPHX_DISABLE_TILES=1 in the environment (A/B testing)
+	bool        tiling_inline; // SPHX_TILING_INLINE set in the environment when the context was created: no side stream
+	bool        side_priority; // SPHX_SIDE_PRIORITY set ...: the side stream at the highest priority
 	bool        neibs_mfma;    // SPHX_NEIBS_MFMA=1 in the environment when the context was created: the list build's prepass on the matrix cores (neibs_build.hip)
 	int         tile_debug;    // SPHX_TILE_DEBUG (timing experiments; only with -DSPHX_TILE_DEBUG_BUILD)
 	unsigned long long *tile_prof;   // ... & 16: phase timers of the tiled forces kernel
@@ -259,6 +261,11 @@ static inline uint32_t round_up_u(uint32_t a, uint32_t b) { return div_up_u(a, b
 
 int sphx_ensure_scratch(sphx_ctx *ctx, uint32_t numParticles);
 int sphx_ensure_tile_lists(sphx_ctx *ctx);
+// ---- the state of the forces tiling: ONE owner on the host side --------------------------------------------------------------
+// sphx_build_neibs_sa (neibs.hip) makes a tiling, the plain forces pass, the SPS stress pass and the three SA_BOUNDARY passes
+// (forces.hip) consume it; nothing else reads tiles_built / tiles_overflow / tiles_cellstart / tiles_neibslist.
+// No tiling until the next build that makes one (a new build, a build that left early, lists that are not there, freed scratch)
+static inline void sphx_tiles_invalidate(sphx_ctx *ctx) { ctx->tiles_built = false; ctx->tiles_overflow = -1; }
 static inline void sphx_tiles_overflow_poll(sphx_ctx *ctx)
 {
 	if (ctx->tiles_overflow == -1 && ctx->ovf_pending && hipEventQuery(ctx->ovf_event) == hipSuccess) {
@@ -266,6 +273,48 @@ static inline void sphx_tiles_overflow_poll(sphx_ctx *ctx)
 		ctx->ovf_pending = false;
 	}
 }
+// may a pass over these buffers run on the tiles?  The tiling belongs to the neighbour list built last by this context from these
+// very buffers, it is not known to have overflowed (the flag's copy is looked for first) and its lists are there
+static inline bool sphx_tiles_current(sphx_ctx *ctx, const uint32_t *cellStart, const uint16_t *neibsList)
+{
+	sphx_tiles_overflow_poll(ctx);
+	return ctx->tiles_built && ctx->tiles_overflow != 1 && ctx->tiles_cellstart == cellStart && ctx->tiles_neibslist == neibsList &&
+		!ctx->disable_tiles && ctx->tile_list != nullptr;
+}
+// the stand-by of a pass that has launched its tiled kernel: the generic kernel behind it, guarded by the device-side overflow
+// flag this points to (every block returns at once unless the tiling overflowed).  NULL: the host has seen the tiling succeed
+// and no stand-by launch is needed at all
+static inline const uint32_t *sphx_tiles_standby_guard(const sphx_ctx *ctx)
+{
+	return ctx->tiles_overflow == 0 ? nullptr : ctx->tile_ctl + 1;
+}
+// Which option sets go through the tiles: the builder's test and the three consumers', side by side.  The builder tiles for a
+// SUPERSET of what the consumers take; each test is kept as it was measured, none of them is derived from another.  Built but
+// not used today: plain runs with several fluids or Ferrari diffusion on a kernel other than Wendland; NEWTONIAN runs with the
+// MONAGHAN / ESPANOL_REVENGA viscous models (their forces are rheology.hip's); the forces pass of SA_BOUNDARY with k-epsilon
+// (its density summation and diffusion do use the tiling); the stress pass of an SPS run with several fluids (its forces pass
+// does, on Wendland); repacking (sphx_repack_launch walks the lists).
+#define SPHX_SA_TILE_FORCES 0              // SA_BOUNDARY engines over the tiles (sphx_sa_tiles_run): which sums the tiled kernel forms
+#define SPHX_SA_TILE_DSUM 1
+#define SPHX_SA_TILE_DIFF 2
+static inline bool sphx_tiles_opts_build(const sphx_ctx *ctx)      // sphx_build_neibs_sa: make a tiling at all?
+{
+	return ctx->params.sph_formulation == SPHX_SPH_F1 && ctx->params.rheologytype <= SPHX_NEWTONIAN &&
+		(ctx->params.boundarytype != SPHX_SA_BOUNDARY ||
+		 (ctx->dev.numfluids == 1 && (ctx->dev.turbmodel == SPHX_LAMINAR_FLOW || ctx->dev.turbmodel == SPHX_KEPSILON)));
+}
+static inline bool sphx_tiles_opts_forces(const DevParams &d)      // sphx_forces_basicstep (DYN / LJ / MK boundaries)
+{
+	// more than one fluid or Ferrari diffusion: tiled for the Wendland kernel only (launch_forces_k, forces.hip)
+	return ((d.numfluids == 1 && d.densitydiff != SPHX_FERRARI) || d.kerneltype == SPHX_WENDLAND) && d.formulation == SPHX_SPH_F1;
+}
+static inline bool sphx_tiles_opts_sa(const DevParams &d, int mode)      // sphx_sa_tiles_run; k-epsilon: the passes that do not involve the model
+{
+	return d.boundarytype == SPHX_SA_BOUNDARY && d.kerneltype == SPHX_WENDLAND && d.numfluids == 1 &&
+		(d.turbmodel == SPHX_LAMINAR_FLOW || (d.turbmodel == SPHX_KEPSILON && mode != SPHX_SA_TILE_FORCES)) &&
+		d.formulation == SPHX_SPH_F1 && d.rheology <= SPHX_NEWTONIAN;
+}
+static inline bool sphx_tiles_opts_stress(const DevParams &d) { return d.numfluids == 1; }      // sphx_calc_visc (SPS)
 // repacking forces (filters.hip), reached through sphx_forces_basicstep(run_mode = SPHX_REPACK)
 #define SPHX_RB_RING 16
 int sphx_fidelity_forces_launch(sphx_ctx *ctx, void *forces, float *cfl,
@@ -280,7 +329,7 @@ int sphx_xsph_launch(sphx_ctx *ctx, void *xsph, const void *pos, const void *vel
 int sphx_neibs_list_launch(sphx_ctx *ctx, uint16_t *neibsList, const void *pos, const void *info, const uint32_t *hash,
 	const uint32_t *cellStart, const uint32_t *cellEnd, const void *vertices, const void *boundElements,
 	void *vertPos0, void *vertPos1, void *vertPos2, uint32_t numParticles, uint32_t particleRangeEnd,
-	float sqinfluenceradius, float boundNlSqInflRad, hipStream_t st);   // neibs_build.hip
+	float sqinfluenceradius, float boundNlSqInflRad, hipStream_t st);   // neibs_build.hip: the whole list (the host emulation of the tests calls it)
 int sphx_neibs_list_launch_part(sphx_ctx *ctx, uint16_t *neibsList, const void *pos, const void *info, const uint32_t *hash,
 	const uint32_t *cellStart, const uint32_t *cellEnd, const void *vertices, const void *boundElements,
 	void *vertPos0, void *vertPos1, void *vertPos2, uint32_t numParticles, uint32_t firstParticle, uint32_t particleRangeEnd,
@@ -288,10 +337,7 @@ int sphx_neibs_list_launch_part(sphx_ctx *ctx, uint16_t *neibsList, const void *
 // the tile lists of the tiles whose LAST home particle lies in [homeFrom, homeTo) (the whole tiling: 0, 0xFFFFFFFF)
 int sphx_tile_lists_launch(sphx_ctx *ctx, const uint16_t *neibsList, const void *info, const uint32_t *hash, const uint32_t *cellStart, bool sa, hipStream_t st,
 	uint32_t homeFrom = 0u, uint32_t homeTo = 0xFFFFFFFFu);
-// SA_BOUNDARY engines over the tiles (forces.hip): which sums the tiled kernel forms
-#define SPHX_SA_TILE_FORCES 0
-#define SPHX_SA_TILE_DSUM 1
-#define SPHX_SA_TILE_DIFF 2
+// SA_BOUNDARY engines over the tiles (forces.hip): mode = SPHX_SA_TILE_*
 int sphx_sa_tiles_run(sphx_ctx *ctx, int mode, void *forces, const void *pos, const void *vel, const void *newPos,
 	const void *info, const uint32_t *hash, const uint32_t *cellStart, const uint16_t *neibsList, const void *gGam,
 	uint32_t numParticles, uint32_t fromParticle, uint32_t toParticle, float dt, hipStream_t stream,
