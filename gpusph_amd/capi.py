@@ -115,6 +115,13 @@ SIGNATURES = {
     "sphx_euler_internal_energy": (_i, [_vp] * 6 + [_u32, _u32, _f, _vp, _f, _vp]),
     "sphx_calc_effvisc": (_i, [_vp] * 9 + [_u32, _u32, _f, _f, _f, _vp]),
     "sphx_forces_basicstep_effvisc": (_i, [_vp] * 10 + [_u32, _u32, _u32, _f, _f, _f, _f, _u32, _i, _i, _f, _vp, _vp]),
+    "sphx_set_granular": (_i, [_vp, C.POINTER(_f), _u32, _f, _f]),
+    "sphx_jacobi_fs_boundary_conditions": (_i, [_vp] * 4 + [_u32, _u32, _f, _vp]),
+    "sphx_jacobi_wall_boundary_conditions": (_i, [_vp, _vp, C.POINTER(_f)] + [_vp] * 6 + [_u32, _u32, _f, _vp]),
+    "sphx_jacobi_build_vectors": (_i, [_vp] * 9 + [_u32, _u32, _vp]),
+    "sphx_jacobi_update_effpres": (_i, [_vp, _vp, C.POINTER(_f)] + [_vp] * 2 + [_u32, _u32, _vp]),
+    "sphx_jacobi_solve": (_i, [_vp] * 8 + [_u32, _u32, _f, C.POINTER(_u32), C.POINTER(_f), C.POINTER(_f), _vp]),
+    "sphx_calc_effvisc_granular": (_i, [_vp] * 10 + [_u32, _u32, _f, _f, _f, _vp]),
     "sphx_compute_density": (_i, [_vp] * 9 + [_u32, _f, _f, _vp]),
     "sphx_forces_basicstep_grenier": (_i, [_vp] * 10 + [_u32, _u32, _u32, _f, _f, _f, _f, _u32, _i, _i, _f, _vp, _vp]),
     "sphx_disable_free_surf_parts": (_i, [_vp, _vp, _vp, _u32, _u32, _vp]),

@@ -26,6 +26,47 @@ __device__ __forceinline__ float kernel_W(const DevParams &p, float r)
 	return val*p.wcoeff;
 }
 
+// F<kerneltype>(r, h) = (1/r) dW/dr: src/cuda/sph_core.cu:140-215 (same forms as kernel_F of forces.hip, IEEE division)
+template<int KERNEL>
+__device__ __forceinline__ float gn_kernel_F(const DevParams &p, float r)
+{
+	const float R = r/p.slength;
+	if (KERNEL == SPHX_WENDLAND) {
+		const float qm2 = R - 2.0f;
+		return qm2*qm2*qm2*p.fcoeff;
+	}
+	if (KERNEL == SPHX_CUBICSPLINE) {
+		float val;
+		if (R < 1.0f) val = (-4.0f + 3.0f*R)/p.slength;   // unused for R >= 2
+		else val = -(-2.0f + R)*(-2.0f + R)/r;
+		return val*p.fcoeff;
+	}
+	if (KERNEL == SPHX_QUADRATIC)
+		return (-2.0f + R)/r*p.fcoeff;
+	return -expf(-R*R)*p.fcoeff;
+}
+
+__device__ __forceinline__ float gn_F(const DevParams &p, float r)
+{
+	switch (p.kerneltype) {
+	case SPHX_CUBICSPLINE: return gn_kernel_F<SPHX_CUBICSPLINE>(p, r);
+	case SPHX_QUADRATIC: return gn_kernel_F<SPHX_QUADRATIC>(p, r);
+	case SPHX_GAUSSIAN: return gn_kernel_F<SPHX_GAUSSIAN>(p, r);
+	default: return gn_kernel_F<SPHX_WENDLAND>(p, r);
+	}
+}
+
+// W of the kernel type of the run
+__device__ __forceinline__ float gn_W(const DevParams &p, float r)
+{
+	switch (p.kerneltype) {
+	case SPHX_CUBICSPLINE: return kernel_W<SPHX_CUBICSPLINE>(p, r);
+	case SPHX_QUADRATIC: return kernel_W<SPHX_QUADRATIC>(p, r);
+	case SPHX_GAUSSIAN: return kernel_W<SPHX_GAUSSIAN>(p, r);
+	default: return kernel_W<SPHX_WENDLAND>(p, r);
+	}
+}
+
 // neiblist_iterator (src/cuda/neibs_iteration.cuh:83-360) over one section of a particle's list:
 // f(neib_index, relPos.x, relPos.y, relPos.z) for every stored neighbour, in list order
 // A: any struct with members pos (float4*), cellStart, neibsList

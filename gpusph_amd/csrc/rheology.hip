@@ -10,37 +10,10 @@
 // in the reference's order, exact powf / expf / division.  Checked against oracle/sph_oracle.c at fp32 tolerance
 // (tests/test_gpu_rheology.py).  Built for SPH_F1, DYN_BOUNDARY, LAMINAR_FLOW + MORRIS, density diffusion NONE / COLAGROSSI /
 // FERRARI, every kernel function; no bodies with force feedback.
+//   sphx_calc_effvisc_granular     the same pass for GRANULAR: the yield stress of the sediment comes from BUFFER_EFFPRES
+//                                  (granular.hip solves it), the viscosity is clamped from both sides, non-fluid slots are left
+//                                  alone; the forces then take the central particle's viscosity for every neighbour
 #include "neib_iter.h"
-
-// F<kerneltype>(r, h) = (1/r) dW/dr: src/cuda/sph_core.cu:140-215 (same forms as kernel_F of forces.hip, IEEE division)
-template<int KERNEL>
-__device__ __forceinline__ float gn_kernel_F(const DevParams &p, float r)
-{
-	const float R = r/p.slength;
-	if (KERNEL == SPHX_WENDLAND) {
-		const float qm2 = R - 2.0f;
-		return qm2*qm2*qm2*p.fcoeff;
-	}
-	if (KERNEL == SPHX_CUBICSPLINE) {
-		float val;
-		if (R < 1.0f) val = (-4.0f + 3.0f*R)/p.slength;   // unused for R >= 2
-		else val = -(-2.0f + R)*(-2.0f + R)/r;
-		return val*p.fcoeff;
-	}
-	if (KERNEL == SPHX_QUADRATIC)
-		return (-2.0f + R)/r*p.fcoeff;
-	return -expf(-R*R)*p.fcoeff;
-}
-
-__device__ __forceinline__ float gn_F(const DevParams &p, float r)
-{
-	switch (p.kerneltype) {
-	case SPHX_CUBICSPLINE: return gn_kernel_F<SPHX_CUBICSPLINE>(p, r);
-	case SPHX_QUADRATIC: return gn_kernel_F<SPHX_QUADRATIC>(p, r);
-	case SPHX_GAUSSIAN: return gn_kernel_F<SPHX_GAUSSIAN>(p, r);
-	default: return gn_kernel_F<SPHX_WENDLAND>(p, r);
-	}
-}
 
 // horner_one_minus_exp_minus_over<8> (src/cuda/visc_kernel.cu:420-451): (1 - exp(-x))/x below x = 1
 __device__ __forceinline__ float horner_one_minus_exp_minus_over8(float x)
@@ -52,10 +25,25 @@ __device__ __forceinline__ float horner_one_minus_exp_minus_over8(float x)
 }
 
 // viscShearTerm + viscYieldTerm + clamp_visc (src/cuda/visc_kernel.cu:454-569)
-__device__ __forceinline__ float effective_visc_value(const DevParams &p, float S, uint32_t fluid)
+// GRANULAR (viscShearTerm<GRANULAR> :536-557, clamp_visc<GRANULAR> :573-579): Newtonian for the pure fluid, tau_y/S with
+// tau_y = 2 sqrt(3) sin(psi)/(3 - sin(psi)) p_eff for the sediment, then clamp(x, lo, hi) = fmaxf(lo, fminf(x, hi)): the upper
+// bound is applied first.  S = 0 with p_eff > 0 gives +inf and S = 0 with p_eff = 0 gives 0/0 = NaN; fminf drops the NaN, so both
+// end at the upper bound (or at the lower one, should it be the larger of the two).  The lower bound is the reference's as it is:
+// visccoeff rho0, with visccoeff the DYNAMIC viscosity (GPUSPH::setViscosityCoefficient stores mu for every rheology but NEWTONIAN)
+__device__ __forceinline__ float effective_visc_value(const DevParams &p, float S, uint32_t fluid, bool sediment = false, float effpres = 0.0f)
 {
 	const int rh = p.rheology;
 	float effvisc = 0.0f;
+	if (rh == SPHX_GRANULAR) {
+		if (p.visccoeff[fluid] != 0.0f) {
+			if (!sediment) effvisc += p.visccoeff[fluid];
+			else {
+				const float tau_y = 3.46410161514f*p.sinpsi[fluid]/(3.0f - p.sinpsi[fluid])*effpres;
+				effvisc += tau_y/S;
+			}
+		}
+		return fmaxf(p.visccoeff[fluid]*p.rho0[fluid], fminf(effvisc, p.limiting_kinvisc*p.rho0[fluid]));
+	}
 	if (p.visccoeff[fluid] != 0.0f) {
 		if (rh >= SPHX_DEKEE_TURCOTTE) effvisc += p.visccoeff[fluid]*expf(-p.visc_nonlinear_param[fluid]*S);
 		else if (rh >= SPHX_POWER_LAW) effvisc += p.visccoeff[fluid]*powf(S, p.visc_nonlinear_param[fluid] - 1);
@@ -84,6 +72,7 @@ struct EffViscArgs {
 	const particleinfo *info;
 	const uint32_t *hash, *cellStart;
 	const neibdata *neibsList;
+	const float *effpres;      // GRANULAR: BUFFER_EFFPRES
 	uint32_t numParticles;
 };
 
@@ -94,9 +83,11 @@ effective_visc_kernel(DevParams p, EffViscArgs a)
 	float kinvisc = 0.0f;
 	if (index < a.numParticles) {
 		const float4 pos = a.pos[index];
-		if (is_active_w(pos.w)) {
+		const particleinfo pinfo = a.info[index];
+		// GRANULAR: no viscosity for non-fluid particles, their slot keeps its value (effectiveViscDevice :673-674)
+		if (is_active_w(pos.w) && !(p.rheology == SPHX_GRANULAR && !IS_FLUID(pinfo))) {
 			const float4 vel = a.vel[index];
-			const uint32_t fluid = FLUID_NUM(a.info[index]);
+			const uint32_t fluid = FLUID_NUM(pinfo);
 			const int3 gridPos = grid_pos_from_hash(p, a.hash[index] & CELLTYPE_BITMASK);
 			float dvx[3] = {0, 0, 0}, dvy[3] = {0, 0, 0}, dvz[3] = {0, 0, 0};
 			// shearRate<MIXED_TENSOR> (:307-367): every neighbour, fluid then boundary (for_every_neib, non-SA)
@@ -120,7 +111,8 @@ effective_visc_kernel(DevParams p, EffViscArgs a)
 			diag_terms *= 2.0f;
 			const float off_terms = txy*txy + txz*txz + tyz*tyz;
 			const float S = sqrtf(diag_terms + off_terms);
-			const float effvisc = effective_visc_value(p, S, fluid);
+			const float effvisc = (p.rheology == SPHX_GRANULAR) ?
+				effective_visc_value(p, S, fluid, IS_SEDIMENT(pinfo) != 0, a.effpres[index]) : effective_visc_value(p, S, fluid);
 			kinvisc = effvisc/((vel.w + 1.0f)*p.rho0[fluid]);
 			a.effvisc[index] = (p.compvisc == SPHX_KINEMATIC) ? kinvisc : effvisc;
 		}
@@ -134,19 +126,22 @@ effective_visc_kernel(DevParams p, EffViscArgs a)
 static int gn_check(const sphx_ctx *ctx, const char *who)
 {
 	SPHX_REQUIRE(ctx && ctx->have_params, "sphx (generalized Newtonian): constants not set");
-	if (ctx->params.rheologytype <= SPHX_NEWTONIAN || ctx->params.rheologytype == SPHX_GRANULAR)
+	if (ctx->params.rheologytype <= SPHX_NEWTONIAN)
 		return sphx_set_error(SPHX_ERR_INVALID, who);
 	return SPHX_OK;
 }
 
-extern "C" int sphx_calc_effvisc(sphx_ctx *ctx, float *effvisc, float *h_max_kinvisc,
+static int calc_effvisc(sphx_ctx *ctx, float *effvisc, float *h_max_kinvisc,
 	const void *pos, const void *vel, const void *info, const uint32_t *hash,
-	const uint32_t *cellStart, const uint16_t *neibsList,
+	const uint32_t *cellStart, const uint16_t *neibsList, const float *effpres,
 	uint32_t numParticles, uint32_t particleRangeEnd, float deltap, float slength, float influenceradius, void *stream)
 {
 	(void)numParticles; (void)deltap;
 	int rc = gn_check(ctx, "sphx_calc_effvisc: the rheology needs no effective viscosity (NEEDS_EFFECTIVE_VISC)");
 	if (rc != SPHX_OK) return rc;
+	if ((ctx->params.rheologytype == SPHX_GRANULAR) != (effpres != nullptr))
+		return sphx_set_error(SPHX_ERR_INVALID, "sphx_calc_effvisc: GRANULAR reads BUFFER_EFFPRES (sphx_calc_effvisc_granular), the other rheologies do not");
+	if (effpres) SPHX_REQUIRE(ctx->gr.set, "sphx_calc_effvisc_granular: sphx_set_granular has not been called");
 	SPHX_REQUIRE(effvisc && pos && vel && info && hash && cellStart && neibsList, "sphx_calc_effvisc: missing buffer");
 	SPHX_REQUIRE(slength == ctx->params.slength && influenceradius == ctx->params.influenceradius,
 		"sphx_calc_effvisc: slength / influenceradius differ from the uploaded constants");
@@ -157,6 +152,7 @@ extern "C" int sphx_calc_effvisc(sphx_ctx *ctx, float *effvisc, float *h_max_kin
 		EffViscArgs a = {};
 		a.effvisc = effvisc; a.maxKinvisc = d_max; a.pos = (const float4*)pos; a.vel = (const float4*)vel;
 		a.info = (const particleinfo*)info; a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList;
+		a.effpres = effpres;
 		a.numParticles = particleRangeEnd;
 		effective_visc_kernel<<<div_up_u(particleRangeEnd, 128), 128, 0, st>>>(ctx->dev, a);
 		SPHX_LAUNCH_CHECK("effective_visc_kernel");
@@ -168,6 +164,25 @@ extern "C" int sphx_calc_effvisc(sphx_ctx *ctx, float *effvisc, float *h_max_kin
 		*h_max_kinvisc = (ctx->params.simflags & SPHX_ENABLE_DTADAPT) ? m : __builtin_nanf("");
 	}
 	return SPHX_OK;
+}
+
+extern "C" int sphx_calc_effvisc(sphx_ctx *ctx, float *effvisc, float *h_max_kinvisc,
+	const void *pos, const void *vel, const void *info, const uint32_t *hash,
+	const uint32_t *cellStart, const uint16_t *neibsList,
+	uint32_t numParticles, uint32_t particleRangeEnd, float deltap, float slength, float influenceradius, void *stream)
+{
+	return calc_effvisc(ctx, effvisc, h_max_kinvisc, pos, vel, info, hash, cellStart, neibsList, nullptr, numParticles, particleRangeEnd,
+		deltap, slength, influenceradius, stream);
+}
+
+extern "C" int sphx_calc_effvisc_granular(sphx_ctx *ctx, float *effvisc, float *h_max_kinvisc,
+	const void *pos, const void *vel, const void *info, const uint32_t *hash,
+	const uint32_t *cellStart, const uint16_t *neibsList, const float *effpres,
+	uint32_t numParticles, uint32_t particleRangeEnd, float deltap, float slength, float influenceradius, void *stream)
+{
+	SPHX_REQUIRE(effpres != nullptr, "sphx_calc_effvisc_granular: missing buffer");
+	return calc_effvisc(ctx, effvisc, h_max_kinvisc, pos, vel, info, hash, cellStart, neibsList, effpres, numParticles, particleRangeEnd,
+		deltap, slength, influenceradius, stream);
 }
 
 // what the pair loop needs from a particle besides position and velocity, evaluated once per particle instead of once per pair
@@ -299,7 +314,8 @@ gn_forces_kernel(DevParams p, GnForcesArgs a)
 					const float cv = 5*visc_thirds - avb, cr = 5*(visc_thirds + avb)*vel_dot_pos/pos_den;
 					dx += coeff*(cv*vx + cr*rx); dy += coeff*(cv*vy + cr*ry); dz += coeff*(cv*vz + cr*rz);
 				} else if (viscous) {
-					const float vf = sa_visc_avg(p, p_visc, nrow.w, p_rho, n_rho, nmass)*f;
+					// GRANULAR: the central particle's viscosity for every neighbour (forces_kernel.def:667-678; boundary slots hold none)
+					const float vf = sa_visc_avg(p, p_visc, p.rheology == SPHX_GRANULAR ? p_visc : nrow.w, p_rho, n_rho, nmass)*f;
 					if (p.viscmodel == SPHX_MONAGHAN) {      // along the relative position, approaching pairs only (:2531-2562)
 						const float den = sa_dot3(rx, ry, rz, rx, ry, rz) + p.epsartvisc;
 						const float c = vel_dot_pos < 0 ? p.monaghan_visc_coeff*vel_dot_pos/den : 0.0f;

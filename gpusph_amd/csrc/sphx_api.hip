@@ -90,6 +90,18 @@ static void free_scratch(sphx_ctx *ctx)
 	sphx_tiles_invalidate(ctx);
 }
 
+// the scratch of sphx_jacobi_solve (granular.hip) and its control words
+static void free_granular(sphx_ctx *ctx)
+{
+	GranularState &g = ctx->gr;
+	void *dev[] = { g.ctl, g.rows_int, g.rows_wall, g.cnt_int, g.cnt_wall, g.diag, g.pres2, g.ent_int, g.ent_wall_j, g.ent_wall_ab };
+	for (void *q : dev) if (q) (void)hipFree(q);
+	if (g.ctl_host) (void)hipHostFree(g.ctl_host);
+	g.ctl = g.ctl_host = g.rows_int = g.rows_wall = g.cnt_int = g.cnt_wall = nullptr;
+	g.diag = nullptr; g.pres2 = nullptr; g.ent_int = nullptr; g.ent_wall_j = nullptr; g.ent_wall_ab = nullptr;
+	g.rows_cap = 0; g.ent_int_cap = g.ent_wall_cap = 0;
+}
+
 extern "C" void sphx_destroy(sphx_ctx *ctx)
 {
 	if (!ctx) return;
@@ -108,6 +120,7 @@ extern "C" void sphx_destroy(sphx_ctx *ctx)
 	if (ctx->list_part_events) for (int k = 0; k < SPHX_LIST_PARTS_MAX; ++k) (void)hipEventDestroy(ctx->list_part[k]);
 	if (ctx->dem) (void)hipFree(ctx->dem);
 	if (ctx->open_rows) (void)hipFree(ctx->open_rows);
+	free_granular(ctx);
 	delete ctx->forces_events;
 	delete ctx;
 }
@@ -274,8 +287,20 @@ extern "C" int sphx_set_constants(sphx_ctx *ctx, const sphx_params *sp)
 	if (sp->densitydiffusiontype != SPHX_DENSITY_DIFFUSION_NONE && sp->densitydiffusiontype != SPHX_COLAGROSSI &&
 		sp->densitydiffusiontype != SPHX_FERRARI && sp->boundarytype != SPHX_SA_BOUNDARY)
 		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: Brezzi density diffusion (an SA_BOUNDARY option in the reference's problems) is not built");
-	if (sp->rheologytype < SPHX_INVISCID || sp->rheologytype > SPHX_ZHU || sp->rheologytype == SPHX_GRANULAR)
-		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: INVISCID, NEWTONIAN and the generalized Newtonian rheologies (BINGHAM .. ZHU) are built, GRANULAR is not");
+	if (sp->rheologytype < SPHX_INVISCID || sp->rheologytype > SPHX_ZHU)
+		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: INVISCID, NEWTONIAN, GRANULAR and the generalized Newtonian rheologies (BINGHAM .. ZHU) are built");
+	if (sp->rheologytype == SPHX_GRANULAR) {
+		// granular.hip + the GRANULAR branches of rheology.hip: the option set of DamBreakMobileBed.cu and of Lithostatic.inc with
+		// its DYN boundary (SA walls feed the Jacobi vectors through boundary elements, LJ has no wall rows at all: not built)
+		if (sp->sph_formulation != SPHX_SPH_HA || sp->boundarytype != SPHX_DYN_BOUNDARY || sp->turbmodel != SPHX_LAMINAR_FLOW)
+			return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: GRANULAR is built for SPH_HA, DYN_BOUNDARY and LAMINAR_FLOW");
+		if (sp->viscmodel != SPHX_MORRIS || sp->compvisc != SPHX_KINEMATIC || sp->avgop != SPHX_HARMONIC)
+			return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: GRANULAR is built for the MORRIS viscous model, KINEMATIC computational viscosity and harmonic averaging");
+		if (!(sp->simflags & SPHX_ENABLE_MULTIFLUID))
+			return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: GRANULAR is built with ENABLE_MULTIFLUID");
+		if (sp->simflags & (SPHX_ENABLE_XSPH | SPHX_ENABLE_MOVING_BODIES))
+			return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: GRANULAR is built without XSPH and without moving bodies");
+	}
 	if (sp->rheologytype > SPHX_NEWTONIAN) {
 		// rheology.hip: effective viscosity + the forces that read it
 		if ((sp->sph_formulation != SPHX_SPH_F1 && sp->sph_formulation != SPHX_SPH_HA) || sp->boundarytype != SPHX_DYN_BOUNDARY || sp->turbmodel != SPHX_LAMINAR_FLOW)
@@ -367,6 +392,7 @@ extern "C" int sphx_set_constants(sphx_ctx *ctx, const sphx_params *sp)
 		d.visc_regularization_param[f] = sp->visc_regularization_param[f];
 	}
 	d.limiting_kinvisc = sp->limiting_kinvisc;
+	for (int f = 0; f < SPHX_MAX_FLUIDS; ++f) d.sinpsi[f] = ctx->gr.sinpsi[f];      // sphx_set_granular, in either order
 	d.ewres = sp->ewres; d.nsres = sp->nsres; d.demdx = sp->demdx; d.demdy = sp->demdy; d.demzmin = sp->demzmin;
 	d.wo_z = sp->worldOrigin[2];
 	d.viscmodel = sp->viscmodel; d.monaghan_visc_coeff = sp->monaghan_visc_coeff;

@@ -29,6 +29,7 @@ enum { PT_FLUID = 0, PT_BOUNDARY = 1, PT_VERTEX = 2, PT_TESTPOINT = 3, PT_NONE =
 #define FG_MOVING_BOUNDARY   (PART_FLAG_START << 1)
 #define FG_SURFACE           (PART_FLAG_START << 6)
 #define FG_INTERFACE         (PART_FLAG_START << 7)
+#define FG_SEDIMENT          (PART_FLAG_START << 8)   // granular rheology + effective pressure (src/particleinfo.h:160)
 
 #define SPHX_BLOCK_FORCES 128   // one CFL entry per 128 particles (getFmaxElements contract)
 
@@ -100,6 +101,7 @@ struct DevParams {
 	float    epsinterface;                   // SPH_GRENIER interface term
 	float    yield_strength[SPHX_MAX_FLUIDS], visc_nonlinear_param[SPHX_MAX_FLUIDS], visc_regularization_param[SPHX_MAX_FLUIDS];
 	float    limiting_kinvisc;               // generalized Newtonian rheologies
+	float    sinpsi[SPHX_MAX_FLUIDS];        // GRANULAR: sine of the internal friction angle per fluid (sphx_set_granular)
 	float    ewres, nsres, demdx, demdy, demzmin, wo_z;   // ENABLE_DEM (+ d_worldOrigin.z)
 	const float *dem; int dem_w, dem_h;      // the height map (sphx_set_dem), row-major [h][w]
 	int      viscmodel; float monaghan_visc_coeff; float visc2coeff[SPHX_MAX_FLUIDS];   // visc_model<MONAGHAN | ESPANOL_REVENGA>
@@ -140,6 +142,26 @@ struct NeibsSpread { int maxFluidBoundaryNeibs, maxVertexNeibs; unsigned long lo
 
 #define SPHX_LIST_PARTS_MAX 16
 #define SPHX_LIST_PARTS_DEFAULT 1
+// GRANULAR: what sphx_set_granular holds (it outlives a new sphx_set_constants, like the planes), and the scratch of
+// sphx_jacobi_solve (granular.hip): the compact rows that iterate and their stored list entries, column-major
+struct GranularState {
+	bool     set;
+	float    sinpsi[SPHX_MAX_FLUIDS];
+	uint32_t maxiter;
+	float    backerr, residual;
+	uint32_t *ctl;            // [16] device words, see JC_* in granular.hip
+	uint32_t *ctl_host;       // [16] pinned copy
+	uint32_t *rows_int, *rows_wall;      // [rows_cap] particle index of every compact row
+	uint32_t *cnt_int, *cnt_wall;        // [rows_cap] stored entries of every compact row
+	float2   *diag;                      // [rows_cap] {D, reference pressure of the residual} of every sediment-interior row
+	float    *pres2;                     // [rows_cap] the second pressure array of the Jacobi sweeps
+	uint32_t rows_cap;
+	uint2    *ent_int;                   // [ent_int_cap] {neighbour | JE_RHS, bits of c}
+	uint32_t *ent_wall_j;                // [ent_wall_cap] neighbour
+	float2   *ent_wall_ab;               // [ent_wall_cap] {a, b}
+	size_t   ent_int_cap, ent_wall_cap;
+};
+
 struct sphx_ctx {
 	int         device;
 	bool        have_params;
@@ -246,6 +268,7 @@ struct sphx_ctx {
 	// context, in stream order)
 	uint32_t   *open_rows;
 	uint32_t    open_rows_cap;
+	GranularState gr;
 };
 
 // ---- error plumbing ---------------------------------------------------------------------------
@@ -358,6 +381,8 @@ int sphx_repack_launch(sphx_ctx *ctx, void *forces, float *cfl, void *rbforces, 
 #define IS_FLOATING(f)     ((f).x & (FG_MOVING_BOUNDARY | FG_COMPUTE_FORCE))
 #define HAS_COMPUTE_FORCE(f) ((f).x & FG_COMPUTE_FORCE)
 #define IS_SURFACE(f)      ((f).x & FG_SURFACE)
+#define IS_INTERFACE(f)    ((f).x & FG_INTERFACE)
+#define IS_SEDIMENT(f)     ((f).x & FG_SEDIMENT)
 #define FLUID_NUM(f)       ((f).y >> 12)
 #define OBJECT_NUM(f)      ((f).y & 0xfffu)
 

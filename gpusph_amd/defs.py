@@ -49,6 +49,7 @@ FG_VELOCITY_DRIVEN = 1 << 7
 FG_CORNER = 1 << 8
 FG_SURFACE = 1 << 9
 FG_INTERFACE = 1 << 10
+FG_SEDIMENT = 1 << 11       # granular rheology + effective pressure (src/particleinfo.h:160)
 # cell types / hash
 CELLTYPE_INNER_CELL, CELLTYPE_INNER_EDGE_CELL, CELLTYPE_OUTER_EDGE_CELL, CELLTYPE_OUTER_CELL = 0, 1, 2, 3
 CELLTYPE_BITMASK = 0x3FFFFFFF

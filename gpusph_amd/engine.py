@@ -217,6 +217,8 @@ class TimestepEngine(MultiGpuEngine):
         """HotFile::save of the current state (src/writers/HotFile.cc:86-118); readable by GPUSPH --resume and by
         the reference's scripts/hotdiff.py.  One body record per body, from the LIVE kinematic data (writeBody :285-340)."""
         from . import hotfile
+        if getattr(self, "granular", False):      # BUFFER_EFFPRES is state a resumed run needs; its place in the file is not built
+            raise NotImplementedError("HotFile checkpoints of a run with the GRANULAR rheology are not built")
         st = self.download()
         bodies = []
         if self.num_bodies_parts:
@@ -252,6 +254,8 @@ class TimestepEngine(MultiGpuEngine):
         the kinematic data of the moving bodies (readBody) and the centres of rotation of both engines."""
         self._rows_for = None      # the velocity buffer may be rewritten behind torch's back (multigpu.py, _rows_for)
         from . import hotfile
+        if getattr(self, "granular", False):
+            raise NotImplementedError("HotFile checkpoints of a run with the GRANULAR rheology are not built")
         hf = hotfile.read_hotfile(path)
         a = hf["arrays"]
         n = hf["particles"]

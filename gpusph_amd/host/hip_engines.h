@@ -191,6 +191,12 @@ public:
 		sphx_params p;
 		fill_params(p, sp, pp, worldOrigin, gridSize, cellSize, allocatedParticles);
 		sphx_ctx *c = ctx();
+		if (sp->rheologytype == GRANULAR) {
+			// d_sinpsi (src/cuda/visc.cu setconstants) and the thresholds of JACOBI_STOP_CRITERION (src/GPUSPH.cc:2314-2316)
+			float sinpsi[SPHX_MAX_FLUIDS];
+			for (size_t f = 0; f < SPHX_MAX_FLUIDS; ++f) sinpsi[f] = f < pp->sinpsi.size() ? pp->sinpsi[f] : NAN;
+			sphx_throw(sphx_set_granular(c, sinpsi, sp->jacobi_maxiter, sp->jacobi_backerr, sp->jacobi_residual));
+		}
 		sphx_throw(sphx_set_constants(c, &p));
 		sphx_throw(sphx_reserve(c, (uint32_t)allocatedParticles));
 		std::lock_guard<std::mutex> guard(m_lock);
@@ -569,8 +575,15 @@ public:
 		const uint particleRangeEnd, const float deltap, const float slength, const float influenceradius)
 	{
 		const sphx_params &P = m_c->params();
-		if (P.rheologytype == GRANULAR)
-			sphx_not_built("calc_visc for the granular rheology");
+		if (P.rheologytype == GRANULAR) {
+			// ... with the yield stress of the sediment from BUFFER_EFFPRES (viscShearTerm<GRANULAR>, src/cuda/visc_kernel.cu:536-557)
+			float max_kinvisc = NAN;
+			sphx_throw(sphx_calc_effvisc_granular(m_c->ctx(), bufwrite.getData<BUFFER_EFFVISC>(), &max_kinvisc,
+				bufread.getData<BUFFER_POS>(), bufread.getData<BUFFER_VEL>(), bufread.getData<BUFFER_INFO>(),
+				bufread.getData<BUFFER_HASH>(), bufread.getData<BUFFER_CELLSTART>(), bufread.getData<BUFFER_NEIBSLIST>(),
+				bufread.getData<BUFFER_EFFPRES>(), numParticles, particleRangeEnd, deltap, slength, influenceradius, NULL));
+			return max_kinvisc;
+		}
 		if (NEEDS_EFFECTIVE_VISC(P.rheologytype)) {
 			// effective viscosity of the generalized Newtonian rheologies (src/cuda/visc.cu:86-170): BUFFER_EFFVISC written, the
 			// largest kinematic viscosity returned for the viscous limit of dt
@@ -593,14 +606,39 @@ public:
 		return NAN;
 	}
 
-	void enforce_jacobi_fs_boundary_conditions(const BufferList&, BufferList&, const uint, const uint, const float, const float, const float)
-	{ sphx_not_built("enforce_jacobi_fs_boundary_conditions (GRANULAR rheology)"); }
-	float enforce_jacobi_wall_boundary_conditions(const BufferList&, BufferList&, const uint, const uint, const float, const float, const float)
-	{ sphx_not_built("enforce_jacobi_wall_boundary_conditions (GRANULAR rheology)"); }
-	void build_jacobi_vectors(const BufferList&, BufferList&, const uint, const uint, const float, const float, const float)
-	{ sphx_not_built("build_jacobi_vectors (GRANULAR rheology)"); }
-	float update_jacobi_effpres(const BufferList&, BufferList&, const uint, const uint, const float, const float, const float)
-	{ sphx_not_built("update_jacobi_effpres (GRANULAR rheology)"); }
+	// the four passes of the effective-pressure Jacobi solver (src/cuda/visc.cu:257-660), driven by the integrator's loop
+	void enforce_jacobi_fs_boundary_conditions(const BufferList& bufread, BufferList& bufwrite, const uint numParticles,
+		const uint particleRangeEnd, const float deltap, const float, const float)
+	{
+		sphx_throw(sphx_jacobi_fs_boundary_conditions(m_c->ctx(), bufwrite.getData<BUFFER_EFFPRES>(), bufread.getData<BUFFER_POS>(),
+			bufread.getData<BUFFER_INFO>(), numParticles, particleRangeEnd, deltap, NULL));
+	}
+	float enforce_jacobi_wall_boundary_conditions(const BufferList& bufread, BufferList& bufwrite, const uint numParticles,
+		const uint particleRangeEnd, const float deltap, const float, const float)
+	{
+		float backerr = 0;
+		sphx_throw(sphx_jacobi_wall_boundary_conditions(m_c->ctx(), bufwrite.getData<BUFFER_EFFPRES>(), &backerr,
+			bufread.getData<BUFFER_POS>(), bufread.getData<BUFFER_VEL>(), bufread.getData<BUFFER_INFO>(),
+			bufread.getData<BUFFER_HASH>(), bufread.getData<BUFFER_CELLSTART>(), bufread.getData<BUFFER_NEIBSLIST>(),
+			numParticles, particleRangeEnd, deltap, NULL));
+		return backerr;
+	}
+	void build_jacobi_vectors(const BufferList& bufread, BufferList& bufwrite, const uint numParticles,
+		const uint particleRangeEnd, const float, const float, const float)
+	{
+		sphx_throw(sphx_jacobi_build_vectors(m_c->ctx(), bufwrite.getData<BUFFER_JACOBI>(), bufread.getData<BUFFER_EFFPRES>(),
+			bufread.getData<BUFFER_POS>(), bufread.getData<BUFFER_VEL>(), bufread.getData<BUFFER_INFO>(),
+			bufread.getData<BUFFER_HASH>(), bufread.getData<BUFFER_CELLSTART>(), bufread.getData<BUFFER_NEIBSLIST>(),
+			numParticles, particleRangeEnd, NULL));
+	}
+	float update_jacobi_effpres(const BufferList& bufread, BufferList& bufwrite, const uint numParticles,
+		const uint particleRangeEnd, const float, const float, const float)
+	{
+		float residual = 0;
+		sphx_throw(sphx_jacobi_update_effpres(m_c->ctx(), bufwrite.getData<BUFFER_EFFPRES>(), &residual,
+			bufread.getData<BUFFER_JACOBI>(), bufread.getData<BUFFER_INFO>(), numParticles, particleRangeEnd, NULL));
+		return residual;
+	}
 };
 
 // ---- predictor-corrector integration engine (CUDAPredCorrEngine, src/cuda/euler.cu:40-395) ----

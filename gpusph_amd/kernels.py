@@ -23,6 +23,9 @@ class HipKernels:
         self.params = problem.sphx_params(alloc)
         self.ctx.set_constants(self.params)
         self.ctx.reserve(alloc)
+        if problem.simparams.rheologytype == D.GRANULAR:
+            self.set_granular(problem.physparams.sinpsi, problem.simparams.jacobi_maxiter, problem.simparams.jacobi_backerr,
+                              problem.simparams.jacobi_residual)
         if getattr(problem, "planes", None):
             nrm, gpos, lpos = problem.plane_tables()
             capi.check(self.lib.sphx_set_planes(self.ctx.handle, nrm.ctypes.data, gpos.ctypes.data, lpos.ctypes.data, len(nrm)))
@@ -345,6 +348,59 @@ class HipKernels:
                                                           P.dtadaptfactor, P.influenceradius, cfl_offset, D.SIMULATE, 1, 0.0,
                                                           C.byref(nb), self._s()))
         return int(nb.value)
+
+    # ---- GRANULAR (granular.hip, rheology.hip): BUFFER_EFFPRES and its Jacobi solve
+    def set_granular(self, sinpsi, maxiter, backerr, residual):
+        arr = (C.c_float * 4)(*([float("nan")] * 4))
+        for f, v in enumerate(sinpsi):
+            arr[f] = float(np.float32(v))
+        capi.check(self.lib.sphx_set_granular(self.ctx.handle, arr, int(maxiter), float(np.float32(backerr)), float(np.float32(residual))))
+
+    def jacobi_fs_boundary_conditions(self, effpres, pos, info, n, range_end):
+        p = capi.ptr
+        capi.check(self.lib.sphx_jacobi_fs_boundary_conditions(self.ctx.handle, p(effpres), p(pos), p(info), n, range_end,
+                                                               self.params.deltap, self._s()))
+
+    def jacobi_wall_boundary_conditions(self, effpres, pos, vel, info, hash_, cellStart, neibslist, n, range_end):
+        """returns the largest backward error of the wall rows (one host synchronisation)"""
+        p = capi.ptr
+        err = C.c_float(0.0)
+        capi.check(self.lib.sphx_jacobi_wall_boundary_conditions(self.ctx.handle, p(effpres), C.byref(err), p(pos), p(vel), p(info), p(hash_),
+                                                                 p(cellStart), p(neibslist), n, range_end, self.params.deltap, self._s()))
+        return err.value
+
+    def jacobi_build_vectors(self, jacobi, effpres, pos, vel, info, hash_, cellStart, neibslist, n, range_end):
+        p = capi.ptr
+        capi.check(self.lib.sphx_jacobi_build_vectors(self.ctx.handle, p(jacobi), p(effpres), p(pos), p(vel), p(info), p(hash_),
+                                                      p(cellStart), p(neibslist), n, range_end, self._s()))
+
+    def jacobi_update_effpres(self, effpres, jacobi, info, n, range_end):
+        """returns the largest residual of the sediment-interior rows (one host synchronisation)"""
+        p = capi.ptr
+        res = C.c_float(0.0)
+        capi.check(self.lib.sphx_jacobi_update_effpres(self.ctx.handle, p(effpres), C.byref(res), p(jacobi), p(info), n, range_end,
+                                                       self._s()))
+        return res.value
+
+    def jacobi_solve(self, effpres, pos, vel, info, hash_, cellStart, neibslist, n, range_end):
+        """one whole solve of BUFFER_EFFPRES in place -> (h_jacobiCounter, backward error, residual) of the stop test that fired"""
+        p = capi.ptr
+        it, err, res = C.c_uint32(0), C.c_float(0.0), C.c_float(0.0)
+        capi.check(self.lib.sphx_jacobi_solve(self.ctx.handle, p(effpres), p(pos), p(vel), p(info), p(hash_), p(cellStart), p(neibslist),
+                                              n, range_end, self.params.deltap, C.byref(it), C.byref(err), C.byref(res), self._s()))
+        return int(it.value), err.value, res.value
+
+    def calc_effvisc_granular(self, effvisc, effpres, pos, vel, info, hash_, cellStart, neibslist, n, range_end):
+        """calc_effvisc for GRANULAR: the yield stress of the sediment from BUFFER_EFFPRES"""
+        p = capi.ptr
+        P = self.params
+        mx = C.c_float(0.0)
+        capi.check(self.lib.sphx_calc_effvisc_granular(self.ctx.handle, p(effvisc), C.byref(mx), p(pos), p(vel), p(info), p(hash_),
+                                                       p(cellStart), p(neibslist), p(effpres), n, range_end, P.deltap, P.slength,
+                                                       P.influenceradius, self._s()))
+        if mx.value == mx.value:
+            self.max_kinvisc = float(mx.value)
+        return float(mx.value)
 
     # ---- SPH_GRENIER (grenier.hip)
     def init_volume(self, vol, pos, vel, info, n):

@@ -244,6 +244,17 @@ class MultiGpuEngine:
             self.dkde = torch.zeros((A, 3), dtype=f32, device=dev)
             self.cfl_keps = torch.zeros_like(self.cfl)
         self.effvisc = torch.zeros(A, dtype=f32, device=dev) if self.effvisc_on else None      # BUFFER_EFFVISC
+        # GRANULAR: BUFFER_EFFPRES is particle state (re-sorted, double buffered for that); it starts from the problem's field and
+        # every solve starts from the last one's result.  Solved at initialisation, after the predictor and after the corrector
+        # (_solve_effpres); single domain: the exchange of the pressure per Jacobi iteration is not built
+        self.granular = self.sp.rheologytype == D.GRANULAR
+        if self.granular:
+            if world > 1:
+                raise NotImplementedError("the GRANULAR rheology is built for a single domain")
+            self.effpres = up(arrs["effpres"], f32, (A,)); self.effpres2 = torch.zeros_like(self.effpres)
+            self.jacobi_iterations = {}      # phase ("init", "predictor", "corrector") -> h_jacobiCounter of its last solve
+            self.jacobi_last = {}            # ... -> (backward error, residual) its stop test saw
+            self.jacobi_max_iterations = 0   # the largest counter of any solve so far
         # ENABLE_INTERNAL_ENERGY: BUFFER_INTERNAL_ENERGY (double buffered, re-sorted; starts from zero: init_internal_energy) and its rate
         self.energy_on = bool(self.sp.simflags & D.ENABLE_INTERNAL_ENERGY)
         if self.energy_on:
@@ -311,6 +322,9 @@ class MultiGpuEngine:
         if self.grenier:
             K.gather_rows(self.vol2, self.vol, self.partindex, n)
             self.vol, self.vol2 = self.vol2, self.vol
+        if self.granular:
+            K.gather_rows(self.effpres2, self.effpres, self.partindex, n)
+            self.effpres, self.effpres2 = self.effpres2, self.effpres
         if self.world == 1:
             if self.track_particle_count:
                 before = self.n_local
@@ -573,6 +587,16 @@ class MultiGpuEngine:
         K.find_cell_start(self.cellStart, self.cellEnd, self.hash, n_int, self.n_local)
 
     # ------------------------------------------------------------------ forces / euler
+    def _solve_effpres(self, phase, pos, vel):
+        """INIT_ / POSTPRED_ / POSTCORR_EFFPRES_PREP and the Jacobi loop behind it (PredictorCorrectorIntegrator.cc:962-1008,
+        1046-1182) on the given state, as one call; the surface and interface flags are those the last
+        postprocess(INTERFACE_DETECTION) left in INFO.  Synchronises (the iteration count comes back)."""
+        it, err, res = self.k.jacobi_solve(self.effpres, pos, vel, self.info, self.hash, self.cellStart, self.neibslist,
+                                           self.n_local, self.n_int)
+        self.jacobi_iterations[phase] = it
+        self.jacobi_last[phase] = (err, res)
+        self.jacobi_max_iterations = max(self.jacobi_max_iterations, it)
+
     def _forces_pass(self, pos, vel, combine_min, run_mode=D.SIMULATE, step=1):
         K = self.k
         # (with bodies: rows of body particles owned by other ranks must read zero in the reduction)
@@ -619,7 +643,11 @@ class MultiGpuEngine:
         elif self.effvisc_on and run_mode == D.SIMULATE:
             # CALC_VISC on the state the forces read (internal particles, then UPDATE_EXTERNAL); its largest kinematic viscosity
             # is the viscous limit of this pass's dt on this device (the dt of the step is the minimum over the devices)
-            K.calc_effvisc(self.effvisc, pos, vel, self.info, self.hash, self.cellStart, self.neibslist, self.n_local, self.n_int)
+            if self.granular:      # the yield stress of the sediment comes from BUFFER_EFFPRES
+                K.calc_effvisc_granular(self.effvisc, self.effpres, pos, vel, self.info, self.hash, self.cellStart, self.neibslist,
+                                        self.n_local, self.n_int)
+            else:
+                K.calc_effvisc(self.effvisc, pos, vel, self.info, self.hash, self.cellStart, self.neibslist, self.n_local, self.n_int)
             if self.world > 1:
                 self._exchange([self.effvisc])
 
@@ -703,6 +731,8 @@ class MultiGpuEngine:
             self.build_neibs()
             if self.sa and self.iterations == 0:     # initialisation step of the boundary conditions (not after a resume)
                 self.sa_boundary_conditions(0)
+            if self.granular and self.iterations == 0:      # INIT_EFFPRES, after the first list build
+                self._solve_effpres("init", self.pos, self.vel)
         n = self.n_local
         if self.iterations > 0:      # FILTER phases: internal particles, then UPDATE_EXTERNAL of the velocity buffer
             for ftype, freq in self.filters:
@@ -734,6 +764,8 @@ class MultiGpuEngine:
             self._sa_post_euler_io(1)
         elif self.sa:
             self._sa_post_euler(1)
+        if self.granular:            # POSTPRED_EFFPRES on the state n*; its result is the field of the state n as well
+            self._solve_effpres("predictor", self.pos2, self.vel2)
         # corrector: forces(step n*) -> n+1 = n + dt f*   (written over n*, then renamed to n)
         self._forces_pass(self.pos2, self.vel2, 1, step=2)
         if self.bodies is not None:
@@ -764,6 +796,8 @@ class MultiGpuEngine:
             self.gradgamma, self.gradgamma2 = self.gradgamma2, self.gradgamma
             if self.sa_moving:
                 self.boundelements, self.boundelements2 = self.boundelements2, self.boundelements
+        if self.granular:            # POSTCORR_EFFPRES on the state n+1
+            self._solve_effpres("corrector", self.pos2, self.vel2)
         if self.bodies is not None:                 # EULER_UPLOAD_OBJECTS_CG in the post-corrector phase (:331-332)
             K.set_body_cg_integration(m)
             self._last_motion = m
@@ -820,5 +854,6 @@ class MultiGpuEngine:
                 "forces": self.forces[:n].cpu().numpy(),
                 **({"vol": self.vol[:n].cpu().numpy()} if self.grenier else {}),
                 **({"energy": self.energy[:n].cpu().numpy()} if self.energy_on else {}),
+                **({"effpres": self.effpres[:n].cpu().numpy()} if self.granular else {}),
                 **({"gradgamma": self.gradgamma[:n].cpu().numpy(), "boundelements": self.boundelements[:n].cpu().numpy()} if self.sa else {}),
                 **({k: v[:n].cpu().numpy() for k, v in self.ke.items()} if self.keps else {})}

@@ -55,6 +55,7 @@ class PhysParams:
     visc_nonlinear_param: list = field(default_factory=list)
     visc_regularization_param: list = field(default_factory=list)
     limiting_kinvisc: float = 1.0e3                         # physparams.h:395
+    sinpsi: list = field(default_factory=list)             # GRANULAR: sine of the internal friction angle per fluid (physparams.h:249)
     rheologytype: int = 0                                   # PhysParams is built for the framework's rheology (physparams.h:380)
     monaghan_visc_coeff: float = 10.0                       # physparams.h:266,396
     bulkvisc: list = field(default_factory=list)            # Espanol & Revenga (physparams.h:176)
@@ -97,7 +98,12 @@ class PhysParams:
         self.bulkvisc.append(float("nan")); self.visc2coeff.append(float("nan"))
         self.visc_nonlinear_param.append(0.0 if self.rheologytype >= D.DEKEE_TURCOTTE else 1.0)
         self.visc_regularization_param.append(1000.0)
+        self.sinpsi.append(float("nan"))                   # physparams.h:483
         return len(self.rho0) - 1
+
+    def set_sinpsi(self, fluid_idx, sinpsi):
+        """physparams.h:693-698"""
+        self.sinpsi[fluid_idx] = float(np.float32(sinpsi))
 
     def update_limiting_kinvisc(self, fluid_idx):
         """physparams.h:599-603"""
@@ -206,6 +212,9 @@ class SimParams:
     repack_maxiter: int = 2000         # simparams.h:308-310
     repack_a: float = 0.1
     repack_alpha: float = 0.01
+    jacobi_maxiter: int = 1000         # effective-pressure Jacobi solver of GRANULAR (simparams.h:244-258,311-313)
+    jacobi_backerr: float = 0.00001
+    jacobi_residual: float = 0.000001
     is_const_visc: object = None       # None: FullViscSpec default (single fluid, NEWTONIAN, not k-epsilon; visc_spec.h:268-272)
 
     def set_smoothing(self, smooth, deltap):

@@ -1320,3 +1320,117 @@ class OpenChannel(Problem):
         self.rb_firstindex = np.zeros(0, dtype=np.int32)
         self.rb_cg_gridpos = np.zeros((0, 3), dtype=np.int32)
         self.rb_cg_pos = np.zeros((0, 3), dtype=np.float32)
+
+
+class LithostaticColumn(Problem):
+    """Mirror of src/problems/Lithostatic.inc with its DYN boundary (the lithostatic equilibrium the reference validates the
+    effective pressure of the GRANULAR rheology with): water over a sediment bed on a DYN_BOUNDARY floor; SPH_HA, GRANULARVISC
+    (GRANULAR + MORRIS, KINEMATIC, harmonic averaging), two fluids, c0 = 10 sqrt(g H), rho0 = 1000 / 1892, sin(psi) = 0.5,
+    jacobi_maxiter 10000 and both thresholds 3e-5 (Lithostatic.inc:48-129).  Periodic in x and y instead of the reference's tank,
+    so a column of a few particles across has no side walls; smoothing factor 1.3 (the reference's 2.0 would need more than three
+    cells across a test-size column).
+    Layout: `columns` lattice columns at (i + 1/2) dp; the floor's dyn_layers layers at z = 0, -dp, ...; sediment layers at
+    z = dp .. ns dp, water layers above; the interface height zi lies half a spacing above the top sediment layer.  Flags and fields
+    as DamBreakMobileBed.cu:166-198 sets them: FG_SEDIMENT below zi, FG_INTERFACE for zi - 2 dp <= z <= zi (the top two sediment
+    layers), the sediment is fluid 1, initial effective pressure max(delta_rho g (dp + zi - z), 0) in the sediment and 0 elsewhere
+    (`lithostatic_init=False`: 0 everywhere, Lithostatic.inc's default); hydrostatic densities, masses scaled by the density
+    (Lithostatic.inc:219-226).  Layers are told apart by their lattice index, so `jitter` (a fraction of dp, fluid particles only)
+    does not move a particle across zi.  `tilt` turns gravity about y by that angle (radians): (g sin, 0, -g cos)."""
+
+    def __init__(self, deltap=0.05, *, columns=(9, 9), sediment_layers=8, water_layers=6, jitter=0.0, tilt=0.0,
+                 density_diffusion=D.DENSITY_DIFFUSION_NONE, kerneltype=D.WENDLAND, lithostatic_init=True, sinpsi=0.5,
+                 limiting_kinvisc=1.0e-2, jacobi_maxiter=10000, jacobi_backerr=3e-5, jacobi_residual=3e-5, sfactor=1.3,
+                 linearization=D.DEFAULT_LINEARIZATION):
+        super().__init__()
+        self.m_name = "LithostaticColumn"
+        sp, pp = self.simparams, self.physparams
+        sp.kerneltype = kerneltype
+        sp.sph_formulation = D.SPH_HA
+        sp.boundarytype = D.DYN_BOUNDARY
+        self.set_viscosity(dict(rheologytype=D.GRANULAR, turbmodel=D.LAMINAR_FLOW, compvisc=D.KINEMATIC, viscmodel=D.MORRIS,
+                                avgop=D.HARMONIC))      # GRANULARVISC (src/visc_spec.h:386-391)
+        sp.densitydiffusiontype = density_diffusion
+        if density_diffusion != D.DENSITY_DIFFUSION_NONE:
+            sp.densityDiffCoeff = 0.5
+        sp.periodicbound = D.PERIODIC_X | D.PERIODIC_Y
+        sp.simflags = D.ENABLE_DTADAPT | D.ENABLE_MULTIFLUID
+        sp.sfactor = sfactor
+        sp.jacobi_maxiter, sp.jacobi_backerr, sp.jacobi_residual = int(jacobi_maxiter), float(jacobi_backerr), float(jacobi_residual)
+        self.linearization = linearization
+        self.set_deltap(deltap)
+        dp = self.m_deltap
+        nx, ny = columns
+        ns, nw = int(sediment_layers), int(water_layers)
+        self.dyn_layers = int(math.ceil(sp.sfactor * sp.kernelradius)) + 1
+        self.zi = (ns + 0.5) * dp                      # interface: half a spacing above the top sediment layer
+        self.z_surface = (ns + nw) * dp                # the top water layer
+        self.z_dirichlet = (ns - 1) * dp               # the lower of the two layers that hold the Dirichlet value
+        H = self.z_surface + dp
+        g = 9.81
+        pp.gravity = (g * math.sin(tilt), 0.0, -g * math.cos(tilt))
+        rho0, rho1, nu0 = 1000.0, 1892.0, 1.0e-6
+        c0 = 10.0 * math.sqrt(g * H)
+        pp.add_fluid(rho0)
+        pp.set_dynamic_visc(0, rho0 * nu0)
+        pp.add_fluid(rho1)
+        pp.set_sinpsi(1, sinpsi)
+        pp.set_kinematic_visc(1, nu0)
+        pp.set_limiting_kinvisc(limiting_kinvisc)
+        pp.set_equation_of_state(0, 7.0, c0)
+        pp.set_equation_of_state(1, 7.0, c0)
+        self.m_origin = np.array([0.0, 0.0, -(self.dyn_layers - 0.5) * dp])
+        self.m_size = np.array([nx * dp, ny * dp, H + 2 * dp]) - np.array([0.0, 0.0, self.m_origin[2]])
+        self.m_maxFall = float(H)
+        self.initialize()
+        ij = (_lattice(0, nx - 1, 0, ny - 1, 0, 0)[:, :2].astype(np.float64) + 0.5) * dp
+        layer = lambda k: np.column_stack([ij, np.full(len(ij), k * dp)])
+        sed = np.concatenate([layer(k) for k in range(1, ns + 1)]) if ns else np.zeros((0, 3))
+        wat = np.concatenate([layer(k) for k in range(ns + 1, ns + nw + 1)]) if nw else np.zeros((0, 3))
+        wall = np.concatenate([layer(-k) for k in range(self.dyn_layers)])
+        n_s, n_w, n_b = len(sed), len(wat), len(wall)
+        pos3 = np.concatenate([sed, wat, wall])
+        ntot = len(pos3)
+        z0 = pos3[:, 2].copy()                          # lattice heights: what flags and initial fields are made from
+        if jitter:
+            rng = np.random.default_rng(2718)
+            nf = n_s + n_w
+            pos3[:nf] += rng.uniform(-jitter * dp, jitter * dp, size=(nf, 3))
+            pos3[:nf, :2] = np.mod(pos3[:nf, :2], self.m_size[:2])
+        is_sed = np.zeros(ntot, dtype=bool); is_sed[:n_s] = True
+        fluid = np.zeros(ntot, dtype=bool); fluid[:n_s + n_w] = True
+        flags = np.where(fluid, D.PT_FLUID, D.PT_BOUNDARY).astype(np.uint16)
+        flags[is_sed] |= D.FG_SEDIMENT
+        flags[fluid & (z0 >= self.zi - 2 * dp) & (z0 <= self.zi)] |= D.FG_INTERFACE
+        fluid_idx = np.where(is_sed, 1, 0).astype(np.uint16)
+        info = make_particleinfo(flags, fluid_idx << 12, np.arange(ntot, dtype=np.uint32))
+        # hydrostatic pressure along gravity's vertical component; the floor particles continue the sediment's profile
+        gz = g * math.cos(tilt)
+        hw = self.z_surface - self.zi
+        below = z0 <= self.zi
+        P = np.where(below, rho0 * gz * hw + rho1 * gz * (self.zi - z0), np.maximum(rho0 * gz * (self.z_surface - z0), 0.0))
+        eos_fluid = np.where(below & ~fluid, 1, fluid_idx)      # which EOS the profile is inverted with
+        B = np.array(pp.bcoeff)[eos_fluid]; gam = np.array(pp.gammacoeff)[eos_fluid]
+        rho_tilde = np.power(P / B + 1.0, 1.0 / gam) - 1.0
+        pos = np.empty((ntot, 4), dtype=np.float64)
+        pos[:, :3] = pos3
+        pos[:, 3] = rho0 * dp ** 3 * np.where(fluid, (rho_tilde + 1.0) * np.array(pp.rho0)[fluid_idx] / rho0, 1.0)
+        vel = np.zeros((ntot, 4), dtype=np.float32)
+        vel[:, 3] = np.where(fluid, rho_tilde, 0.0).astype(np.float32)
+        self.parts = HostParticles(pos, vel, info)
+        self.delta_rho = rho1 - rho0
+        self.effpres0 = np.zeros(ntot, dtype=np.float32)
+        if lithostatic_init:
+            self.effpres0[:n_s] = np.maximum(self.delta_rho * g * (dp + self.zi - z0[:n_s]), 0.0).astype(np.float32)
+        self.num_fluid, self.num_wall, self.num_obstacle = n_s + n_w, n_b, 0
+        self.num_sediment = n_s
+        self.rb_firstindex = np.zeros(0, dtype=np.int32)
+        self.rb_cg_gridpos = np.zeros((0, 3), dtype=np.int32)
+        self.rb_cg_pos = np.zeros((0, 3), dtype=np.float32)
+
+    def copy_to_array(self):
+        arrs = super().copy_to_array()
+        arrs["effpres"] = self.effpres0.copy()          # BUFFER_EFFPRES as initializeParticles leaves it
+        return arrs
+
+    def initial_density(self, pos_global):
+        raise NotImplementedError("LithostaticColumn: the density depends on the particle's phase, not on its position alone")

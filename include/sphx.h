@@ -611,6 +611,57 @@ int sphx_forces_basicstep_effvisc(sphx_ctx *ctx, void *forces, float *cfl,
 	float deltap, float slength, float dtadaptfactor, float influenceradius,
 	uint32_t cflOffset, int run_mode, int step, float dt, uint32_t *h_numBlocks, void *stream);
 
+/* ---- GRANULAR (rheology<GRANULAR> with SPH_HA, DYN_BOUNDARY, LAMINAR_FLOW, MORRIS, KINEMATIC, harmonic averaging and
+ * ENABLE_MULTIFLUID: DamBreakMobileBed, Lithostatic with its DYN boundary) -------------------------------------------------------
+ * The sediment (FG_SEDIMENT) yields at tau_y = 2 sqrt(3) sin(psi)/(3 - sin(psi)) p_eff; the effective pressure p_eff
+ * (BUFFER_EFFPRES, one float per particle, particle state: it travels through the re-sort) is solved by Jacobi iterations at
+ * initialisation, after the predictor and after the corrector (src/integrators/PredictorCorrectorIntegrator.cc:962-1008,1046-1182).
+ *   sphx_set_granular              sinpsi per fluid (src/physparams.h:249) and jacobi_maxiter / jacobi_backerr / jacobi_residual
+ *                                  (src/simparams.h:244-313); survives sphx_set_constants, may be called before or after it
+ *   sphx_jacobi_fs_boundary_conditions    enforce_jacobi_fs_boundary_conditions (src/cuda/visc.cu:271-330,
+ *                                  jacobiFSBoundaryConditionsDevice src/cuda/visc_kernel.cu:813-854): surface / interface sediment
+ *                                  fluid rows get delta_rho |g| deltap
+ *   sphx_jacobi_wall_boundary_conditions  enforce_jacobi_wall_boundary_conditions (visc.cu:351-456, jacobiWallBoundaryConditionsDevice
+ *                                  visc_kernel.cu:856-966): PT_BOUNDARY rows by Shepard interpolation over their sediment fluid
+ *                                  neighbours; *h_backerr (may be NULL: no host synchronisation then) gets the largest backward error
+ *   sphx_jacobi_build_vectors      build_jacobi_vectors (visc.cu:472-568, jacobiBuildVectorsDevice visc_kernel.cu:968-1053): jacobi is
+ *                                  BUFFER_JACOBI, one float4 (D, Rx, B, NaN) per particle; the row of a disabled particle is
+ *                                  (0, 0, 0, 0), which the update pass recognises (the reference leaves such rows as they were)
+ *   sphx_jacobi_update_effpres     update_jacobi_effpres (visc.cu:584-660, jacobiUpdateEffPresDevice visc_kernel.cu:1055-1101):
+ *                                  p = (B - Rx)/D on the sediment-interior rows; *h_residual (may be NULL) gets the largest residual,
+ *                                  reduced from a baseline of 0 (the reference's residual is signed); disabled particles keep theirs
+ *   sphx_jacobi_solve              one whole solve -- preparation (the two boundary passes, JACOBI_RESET_STOP_CRITERION), then build /
+ *                                  update / wall pass / JACOBI_STOP_CRITERION (src/GPUSPH.cc:2295-2320) until the test fires -- with the
+ *                                  pair coefficients stored once per solve and the stop test on the device.  Pressures, *iterations
+ *                                  (h_jacobiCounter when the test fired), *backerr and *residual (the maxima it saw) are bit-equal to
+ *                                  driving the four entry points above.  Synchronises the stream; one solve at a time per context
+ *   sphx_calc_effvisc_granular     sphx_calc_effvisc for GRANULAR (viscShearTerm / clamp_visc<GRANULAR>, visc_kernel.cu:529-579):
+ *                                  reads effpres; non-fluid slots of effvisc keep their value, pure fluid is Newtonian, the result
+ *                                  is clamped to [visccoeff rho0, limiting_kinvisc rho0].  sphx_forces_basicstep_effvisc then takes
+ *                                  the central particle's viscosity for every neighbour (src/cuda/forces_kernel.def:667-678) */
+int sphx_set_granular(sphx_ctx *ctx, const float sinpsi[SPHX_MAX_FLUIDS], uint32_t maxiter, float backerr, float residual);
+int sphx_jacobi_fs_boundary_conditions(sphx_ctx *ctx, float *effpres, const void *pos, const void *info,
+	uint32_t numParticles, uint32_t particleRangeEnd, float deltap, void *stream);
+int sphx_jacobi_wall_boundary_conditions(sphx_ctx *ctx, float *effpres, float *h_backerr,
+	const void *pos, const void *vel, const void *info, const uint32_t *hash,
+	const uint32_t *cellStart, const uint16_t *neibsList,
+	uint32_t numParticles, uint32_t particleRangeEnd, float deltap, void *stream);
+int sphx_jacobi_build_vectors(sphx_ctx *ctx, void *jacobi, const float *effpres,
+	const void *pos, const void *vel, const void *info, const uint32_t *hash,
+	const uint32_t *cellStart, const uint16_t *neibsList,
+	uint32_t numParticles, uint32_t particleRangeEnd, void *stream);
+int sphx_jacobi_update_effpres(sphx_ctx *ctx, float *effpres, float *h_residual, const void *jacobi,
+	const void *info, uint32_t numParticles, uint32_t particleRangeEnd, void *stream);
+int sphx_jacobi_solve(sphx_ctx *ctx, float *effpres,
+	const void *pos, const void *vel, const void *info, const uint32_t *hash,
+	const uint32_t *cellStart, const uint16_t *neibsList,
+	uint32_t numParticles, uint32_t particleRangeEnd, float deltap,
+	uint32_t *iterations, float *backerr, float *residual, void *stream);
+int sphx_calc_effvisc_granular(sphx_ctx *ctx, float *effvisc, float *h_max_kinvisc,
+	const void *pos, const void *vel, const void *info, const uint32_t *hash,
+	const uint32_t *cellStart, const uint16_t *neibsList, const float *effpres,
+	uint32_t numParticles, uint32_t particleRangeEnd, float deltap, float slength, float influenceradius, void *stream);
+
 /* ---- SPH_GRENIER (formulation<SPH_GRENIER>, boundary<DYN_BOUNDARY>: Bubble, LockExchange, RTInstability, OilJet) ----------
  * The volume formulation keeps two more buffers, BUFFER_VOLUME (float4: x initial volume, y log(current/initial), w current
  * volume) and BUFFER_SIGMA (float).
