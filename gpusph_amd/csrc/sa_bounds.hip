@@ -280,6 +280,11 @@ sa_forces_kernel(DevParams p, SaForcesArgs a)
 				float diff_k = 0.0f, diff_e = 0.0f, ce2yap = 1.92f, txx = 0.0f, txy = 0.0f, txz = 0.0f, tyy = 0.0f, tyz = 0.0f, tzz = 0.0f;
 				const bool density_sum = (p.simflags & SPHX_ENABLE_DENSITY_SUM) != 0;
 				const bool newtonian = p.rheology == SPHX_NEWTONIAN;
+				// Ferrari density diffusion in the continuity equation (compute_density_diffusion :1608-1705, Spheric2SA's set): fluid
+				// neighbours and boundary elements contribute, vertices do not (:1600)
+				const bool ferrari = p.densitydiff == SPHX_FERRARI && !density_sum;
+				const float p_sspeed = ferrari ? sa_sound_speed(p, vel.w, fl) : 0.0f;
+				const float sqC0 = ferrari ? p.sscoeff[fl]*p.sscoeff[fl] : 1.0f;
 				// fluid <- fluid and fluid <- vertex: compute_all_pp_interaction with the general specialisations
 				auto particle_pair = [&](bool vertexSection, uint32_t j, const float4 &npos, float rx, float ry, float rz) {
 					if (!is_active_w(npos.w)) return;
@@ -294,7 +299,19 @@ sa_forces_kernel(DevParams p, SaForcesArgs a)
 					const float n_rho = (nvel.w + 1.0f)*p.rho0[nfl];
 					const float n_precalc = KEPS ? (sa_P(p, nvel.w, nfl) + 2.0f*a.tke[j]/n_rho/3.0f)/(n_rho*n_rho) : sa_P(p, nvel.w, nfl)/(n_rho*n_rho);
 					const float nmass = npos.w;
-					if (!density_sum) force.w += nmass*vel_dot_pos*f;
+					if (!density_sum) {
+						float DrDt = nmass*vel_dot_pos*f;
+						if (ferrari && !vertexSection) {      // :1622-1636
+							const float grav_corr = -sa_dot3(p.gravity[0], p.gravity[1], p.gravity[2], rx, ry, rz)*p.rho0[fl]/sqC0;
+							float cx = 0.0f, cy = 0.0f, cz = 0.0f;
+							if (r > 1e-4f*p.slength) {
+								const float sc = fmaxf(p_sspeed, sa_sound_speed(p, nvel.w, nfl))*(p_rho - n_rho + grav_corr)/p_rho/r;
+								cx = sc*rx; cy = sc*ry; cz = sc*rz;
+							}
+							DrDt += p.densityDiffCoeff*nmass*sa_dot3(cx, cy, cz, rx, ry, rz)*f;
+						}
+						force.w += DrDt;
+					}
 					const float s = (p_precalc + n_precalc)*nmass*f;
 					float dx = 0.0f, dy = 0.0f, dz = 0.0f;
 					dx -= s*rx; dy -= s*ry; dz -= s*rz;
@@ -360,6 +377,12 @@ sa_forces_kernel(DevParams p, SaForcesArgs a)
 					if (!density_sum) {
 						float DrDt = 0.0f;
 						DrDt -= p_rho*vn*ggamAS;
+						if (ferrari) {      // :1691-1705: rho and c of the element from its row of the velocity buffer
+							const float grav_corr = -sa_dot3(p.gravity[0], p.gravity[1], p.gravity[2], rx, ry, rz)*p.rho0[fl]/sqC0;
+							const float fc = (r > 1e-4f*p.slength) ?
+								fmaxf(p_sspeed, sa_sound_speed(p, nvel.w, nfl))*(p_rho - n_rho + grav_corr)/r : 0.0f;
+							DrDt -= p.densityDiffCoeff*fc*sa_dot3(rx, ry, rz, be.x, be.y, be.z)*ggamAS;
+						}
 						force.w += DrDt;
 					}
 					const float n_precalc_k = KEPS ? (sa_P(p, nvel.w, nfl) + 2.0f*a.tke[j]/n_rho/3.0f)/(n_rho*n_rho) : n_precalc;
@@ -1050,6 +1073,12 @@ static int sa_forces_check(sphx_ctx *ctx, const char *who)
 		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx_sa: SA forces are built without XSPH and planes");
 	if (q.sph_formulation != SPHX_SPH_F1)
 		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx_sa: SA forces are built for SPH_F1");
+	// density diffusion: Brezzi with the density summation (a pass of its own), Ferrari with the continuity equation (a term of the
+	// forces pass: Spheric2SA's set); Colagrossi has no SA form in the reference either
+	if (q.densitydiffusiontype == SPHX_FERRARI) {
+		if (dsum)
+			return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx_sa: Ferrari density diffusion with SA_BOUNDARY is a term of the continuity equation (ENABLE_GAMMA_QUADRATURE): not built with ENABLE_DENSITY_SUM");
+	} else
 	if (!(q.densitydiffusiontype == SPHX_DENSITY_DIFFUSION_NONE || (dsum && q.densitydiffusiontype == SPHX_BREZZI)))
 		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx_sa: density diffusion with SA_BOUNDARY: Brezzi with density summation only");
 	if (q.turbmodel != SPHX_LAMINAR_FLOW && q.turbmodel != SPHX_KEPSILON && q.rheologytype != SPHX_INVISCID)

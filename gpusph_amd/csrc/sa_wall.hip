@@ -158,6 +158,11 @@ sa_forces_wall_kernel(DevParams p, SaForcesArgs a, const uint32_t *__restrict__ 
 		const float p_precalc = sa_P(p, vel.w, fl)/(p_rho*p_rho);
 		const bool density_sum = (p.simflags & SPHX_ENABLE_DENSITY_SUM) != 0;
 		const bool newtonian = p.rheology == SPHX_NEWTONIAN;
+		// Ferrari diffusion in the continuity equation: the element's share (compute_density_diffusion :1691-1705), formed where its
+		// continuity term is, from the same |grad gamma_as|, and summed over the lanes with it.  Wave-uniform: a scalar branch
+		const bool ferrari = p.densitydiff == SPHX_FERRARI && !density_sum;
+		const float p_sspeed = ferrari ? sa_sound_speed(p, vel.w, fl) : 0.0f;
+		const float gravCoeff = ferrari ? p.rho0[fl]/(p.sscoeff[fl]*p.sscoeff[fl]) : 0.0f;      // g_corr = -(g . r) rho0/c0^2
 		// a.open: a run with open boundaries (sa_forces_kernel<false, true>, see there): the viscous term of a boundary element sees the
 		// relative velocity plus the relative Eulerian velocity (no normal part taken out for the segment of an open face), the gamma CFL
 		// term gains compute_gamma_cfl_open_boundary, and the fluid <- vertex pairs, whose sums the tiled kernel formed with the relative
@@ -214,6 +219,12 @@ sa_forces_wall_kernel(DevParams p, SaForcesArgs a, const uint32_t *__restrict__ 
 				}
 			}
 			if (!density_sum) fw -= p_rho*vn*ggamAS;
+			if (ferrari) {
+				const float gdotr = sa_dot3(p.gravity[0], p.gravity[1], p.gravity[2], rx, ry, rz);
+				const float drho = (p_rho - n_rho) - gdotr*gravCoeff;
+				const float fc = (r > 1e-4f*p.slength) ? fmaxf(p_sspeed, sa_sound_speed(p, nvel.w, nfl))*drho/r : 0.0f;
+				fw -= p.densityDiffCoeff*fc*sa_dot3(rx, ry, rz, be.x, be.y, be.z)*ggamAS;
+			}
 			const float ps = (p_precalc + n_precalc)*n_rho*ggamAS;
 			float dx = ps*be.x, dy = ps*be.y, dz = ps*be.z;
 			if (newtonian) {

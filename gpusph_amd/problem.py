@@ -891,7 +891,11 @@ class SABox(Problem):
     Framework options, list size, deltap and smoothing are StillWaterSA's (src/problems/StillWaterSA.cu:38-57) or, with
     options="StillWaterRepackSA", those of that problem's simulation (src/problems/StillWaterRepackSA.cu:38-44: continuity
     equation instead of density summation, gamma by quadrature, no density diffusion) -- the set the SA forces /
-    integration engines are built for.  Wendland kernel (the only one the reference's SA code supports, src/cuda/gamma.cuh:241-250)."""
+    integration engines are built for.  options="Spheric2SA": the framework line of the reference's SA validation case
+    (src/problems/Spheric2SA.cu:40-48: continuity equation, gamma by quadrature, Ferrari density diffusion as a term of the
+    forces pass) with that problem's ferrariLengthScale / deltap (:50,63); viscosity="KEPSVISC" is its own choice,
+    "DYNAMICVISC" the one its commented-out line offers.  Tank, fluid and list sizes stay this class's.
+    Wendland kernel (the only one the reference's SA code supports, src/cuda/gamma.cuh:241-250)."""
 
     def __init__(self, deltap=0.05, *, l=0.6, w=0.5, h=0.5, H=0.35, viscosity="DYNAMICVISC", jitter=0.0,
                  linearization=D.DEFAULT_LINEARIZATION, options="StillWaterSA"):
@@ -900,6 +904,8 @@ class SABox(Problem):
         sp, pp = self.simparams, self.physparams
         sp.kerneltype = D.WENDLAND
         sp.boundarytype = D.SA_BOUNDARY
+        if viscosity == "KEPSVISC":      # legacy name: DYNAMICVISC + KEPSILON (src/visc_spec.h:379-384)
+            viscosity = dict(rheologytype=D.NEWTONIAN, turbmodel=D.KEPSILON)
         self.set_viscosity(viscosity)
         if options == "StillWaterSA":
             sp.densitydiffusiontype = D.BREZZI
@@ -908,6 +914,9 @@ class SABox(Problem):
         elif options == "StillWaterRepackSA":
             sp.densitydiffusiontype = D.DENSITY_DIFFUSION_NONE
             sp.simflags = D.ENABLE_DTADAPT | D.ENABLE_REPACKING | D.ENABLE_GAMMA_QUADRATURE
+        elif options == "Spheric2SA":
+            sp.densitydiffusiontype = D.FERRARI
+            sp.simflags = D.ENABLE_DTADAPT | D.ENABLE_GAMMA_QUADRATURE
         else:
             raise ValueError(options)
         self.options = options
@@ -915,6 +924,8 @@ class SABox(Problem):
         self.jitter = jitter
         self.set_deltap(deltap)
         dp = self.m_deltap
+        if options == "Spheric2SA":      # initialize() derives densityDiffCoeff = 1e-3 ferrariLengthScale / deltap from it
+            sp.ferrariLengthScale = float(np.float32(0.161)) / float(np.float32(0.02715)) * dp
         self.n_l, self.n_w, self.n_h = (int(round(v / dp)) for v in (l, w, h))
         self.l, self.w, self.h, self.H = self.n_l * dp, self.n_w * dp, self.n_h * dp, float(H)
         self.m_origin = np.full(3, -2.0 * dp)

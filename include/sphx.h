@@ -249,7 +249,13 @@ int sphx_sa_body_pressure_forces(sphx_ctx *ctx, void *forces, void *rbforces, vo
  * gravity, CFL maxima.  Built for solid walls, SPH_F1, laminar Newtonian or inviscid flow, in two forms: the continuity
  * equation with ENABLE_GAMMA_QUADRATURE (StillWaterRepackSA's simulation) and ENABLE_DENSITY_SUM with dynamic gamma
  * (StillWaterSA; then cflGamma = BUFFER_CFL_GAMMA receives the CFL condition of the gamma transport, per particle and, behind
- * round_up(numParticles, 4), per block -- NULL otherwise); everything else answers SPHX_ERR_UNSUPPORTED. */
+ * round_up(numParticles, 4), per block -- NULL otherwise); everything else answers SPHX_ERR_UNSUPPORTED.
+ * Density diffusion: BREZZI belongs to the density summation and is a pass of its own (sphx_sa_compute_density_diffusion).  FERRARI
+ * is taken in the continuity-equation form only (ENABLE_GAMMA_QUADRATURE without ENABLE_DENSITY_SUM: Spheric2SA's set), by this
+ * entry point and by sphx_forces_basicstep_sa_keps alike, as a term of force.w before the division by gamma
+ * (compute_density_diffusion, src/cuda/forces_kernel.def:1608-1705): fluid neighbours and boundary elements (rho and c of an element
+ * from its row of `vel`, the pair's |grad gamma_as|) contribute, vertices do not; the coefficient is densityDiffCoeff.  FERRARI with
+ * ENABLE_DENSITY_SUM, with open boundaries (the *_io entry points) and COLAGROSSI with SA_BOUNDARY answer SPHX_ERR_UNSUPPORTED. */
 int sphx_forces_basicstep_sa(sphx_ctx *ctx, void *forces, float *cfl, float *cflGamma,
 	const void *pos, const void *vel, const void *info, const uint32_t *hash, const uint32_t *cellStart, const uint16_t *neibsList,
 	const void *gGam, const void *boundElements, const void *vertPos0, const void *vertPos1, const void *vertPos2,
@@ -448,7 +454,8 @@ int sphx_sa_vertex_bc(sphx_ctx *ctx, void *vel, const void *gGam, const void *po
  *                             2824-2878,2915-2980,3123-3170): P + 2/3 rho k in the pressure term, laminar + eddy viscosity in the
  *                             volumic MORRIS term, wall shear stress from the law of the wall instead of the laminar wall term,
  *                             DKDE from the boundary sums (the state the reference's last forcesDevice launch leaves), the strain
- *                             production term limited to 0.3 k S; cflKeps = per-block max eddy viscosity
+ *                             production term limited to 0.3 k S; cflKeps = per-block max eddy viscosity; FERRARI diffusion in
+ *                             the continuity-equation form as in sphx_forces_basicstep_sa (force.w only: DKDE does not see it)
  *   sphx_euler_keps           the k-epsilon part of eulerDevice (euler_kernel.def:219-231,262-274,325-337): semi-implicit k and
  *                             epsilon of fluid rows, eulerVel += dt force of wall rows, turbvisc = 0.9 k^2/epsilon of every row;
  *                             dt from d_dt[0]*dt_scale when d_dt is given, like sphx_euler_basicstep
