@@ -108,6 +108,9 @@ SIGNATURES = {
     "sphx_calc_visc": (_i, [_vp] + [_vp] * 10 + [_u32, _u32, _f, _f, _f, _vp]),
     "sphx_filter_process": (_i, [_vp, _i] + [_vp] * 7 + [_u32, _u32, _f, _f, _vp]),
     "sphx_postprocess": (_i, [_vp, _i] + [_vp] * 10 + [_u32, _u32, _f, _f, _vp]),
+    "sphx_postprocess_testpoints_keps": (_i, [_vp] * 9 + [_u32, _u32, _vp]),
+    "sphx_wave_gages": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
+    "sphx_wave_gages_finish": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),
     "sphx_euler_basicstep": (_i, [_vp] + [_vp] * 8 + [_u32, _u32, _f, _vp, _f, _i, _f, _f, _f, _i, _vp]),
     "sphx_euler_basicstep_grenier": (_i, [_vp] + [_vp] * 10 + [_u32, _u32, _f, _vp, _f, _i, _f, _f, _f, _i, _vp]),
     "sphx_init_volume": (_i, [_vp] * 5 + [_u32, _vp]),

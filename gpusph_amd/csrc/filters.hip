@@ -211,6 +211,7 @@ struct PostArgs {
 	particleinfo *infoInOut;   // SURFACE_DETECTION: updated in place
 	float4 *normals;           // SURFACE_DETECTION, optional
 	float cosconeanglefluid, cosconeanglenonfluid;
+	float *tke, *eps;          // TESTPOINTS with SA_BOUNDARY and k-epsilon: averaged in place like the velocity, optional
 };
 
 // calcVortDevice (:58-135)
@@ -295,8 +296,10 @@ int sphx_xsph_launch(sphx_ctx *ctx, void *xsph, const void *pos, const void *vel
 	return SPHX_OK;
 }
 
-// calcTestpointsVelocityDevice (:138-236), non-SA, no k-epsilon buffers
-template<int KERNEL>
+// calcTestpointsVelocityDevice (:135-240).  SA: the instantiation of SA_BOUNDARY contexts, which sums over the vertex section of the
+// test point's list as well (for_each_neib2(PT_FLUID, PT_VERTEX): vertex particles carry mass, density and velocity) and averages
+// k and epsilon with the same weights when their buffers are given (:206-213,222-239)
+template<int KERNEL, bool SA = false>
 __global__ void __launch_bounds__(128)
 testpoints_kernel(DevParams p, FilterArgs a, PostArgs o)
 {
@@ -306,9 +309,9 @@ testpoints_kernel(DevParams p, FilterArgs a, PostArgs o)
 	if (!IS_TESTPOINT(info)) return;
 	const float4 pos = a.pos[index];
 	float4 avg = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-	float alpha = 0.0f;
+	float alpha = 0.0f, tkeavg = 0.0f, epsavg = 0.0f;
 	const int3 gridPos = grid_pos_from_hash(p, a.hash[index] & CELLTYPE_BITMASK);
-	for_each_neib<PT_FLUID>(p, a, index, pos, gridPos, [&](uint32_t j, const float4 &npos, float rx, float ry, float rz) {
+	auto pair = [&](uint32_t j, const float4 &npos, float rx, float ry, float rz) {
 		const float r = sqrtf(rx*rx + ry*ry + rz*rz);
 		if (r < p.influenceradius) {
 			const float4 nvel = o.velInOut[j];
@@ -316,20 +319,33 @@ testpoints_kernel(DevParams p, FilterArgs a, PostArgs o)
 			const float w = kernel_W<KERNEL>(p, r)*npos.w/((nvel.w + 1.0f)*p.rho0[nfl]);
 			avg.x += w*nvel.x; avg.y += w*nvel.y; avg.z += w*nvel.z;
 			avg.w += w*(p.bcoeff[nfl]*(powf(nvel.w + 1.0f, p.gammacoeff[nfl]) - 1.0f));
+			if constexpr (SA) {
+				if (o.tke) tkeavg += w*o.tke[j];
+				if (o.eps) epsavg += w*o.eps[j];
+			}
 			alpha += w;
 		}
-	});
+	};
+	for_each_neib<PT_FLUID>(p, a, index, pos, gridPos, pair);
+	if constexpr (SA) for_each_neib<PT_VERTEX>(p, a, index, pos, gridPos, pair);
 	if (alpha > 1e-5f) {
 		const float inv = 1.0f/alpha;
 		avg.x *= inv; avg.y *= inv; avg.z *= inv; avg.w *= inv;
+		tkeavg *= inv; epsavg *= inv;
 	} else {
 		avg = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+		tkeavg = epsavg = 0.0f;
 	}
 	o.velInOut[index] = avg;
+	if constexpr (SA) {
+		if (o.tke) o.tke[index] = tkeavg;
+		if (o.eps) o.eps[index] = epsavg;
+	}
 }
 
-// calcSurfaceparticleDevice (:239-392), non-SA
-template<int KERNEL>
+// calcSurfaceparticleDevice (:239-392).  SA: the instantiation of SA_BOUNDARY contexts: for_every_neib<SA_BOUNDARY> walks the fluid,
+// the boundary and then the vertex section (src/cuda/neibs_iteration.cuh:341-360), so both loops gain the vertices
+template<int KERNEL, bool SA = false>
 __global__ void __launch_bounds__(128)
 surface_kernel(DevParams p, FilterArgs a, PostArgs o)
 {
@@ -357,6 +373,7 @@ surface_kernel(DevParams p, FilterArgs a, PostArgs o)
 	};
 	for_each_neib<PT_FLUID>(p, a, index, pos, gridPos, first);
 	for_each_neib<PT_BOUNDARY>(p, a, index, pos, gridPos, first);
+	if constexpr (SA) for_each_neib<PT_VERTEX>(p, a, index, pos, gridPos, first);
 	if (p.simflags & SPHX_ENABLE_PLANES)
 		for (uint32_t k = 0; k < p.numplanes; ++k) {
 			const float dx = (gridPos.x - p.plane_gridpos[k][0])*p.cs[0] + (pos.x - p.plane_pos[k][0]);
@@ -381,6 +398,7 @@ surface_kernel(DevParams p, FilterArgs a, PostArgs o)
 	};
 	for_each_neib<PT_FLUID>(p, a, index, pos, gridPos, second);
 	for_each_neib<PT_BOUNDARY>(p, a, index, pos, gridPos, second);
+	if constexpr (SA) for_each_neib<PT_VERTEX>(p, a, index, pos, gridPos, second);
 	if (!nc) info.x |= FG_SURFACE;
 	o.infoInOut[index] = info;
 	if (o.normals) {
@@ -460,13 +478,62 @@ interface_kernel(DevParams p, FilterArgs a, PostArgs o)
 	}
 }
 
-template<int KERNEL>
+// SA: the context has SA_BOUNDARY.  Contexts with LJ / DYN / MK boundaries launch the instantiations they always did (SA = false);
+// the vorticity sums over fluid neighbours only and is one kernel for all of them
+template<int KERNEL, bool SA>
 static void launch_post(int type, dim3 grid, hipStream_t st, const DevParams &p, const FilterArgs &a, const PostArgs &o)
 {
 	if (type == SPHX_VORTICITY) vorticity_kernel<KERNEL><<<grid, 128, 0, st>>>(p, a, o);
-	else if (type == SPHX_TESTPOINTS) testpoints_kernel<KERNEL><<<grid, 128, 0, st>>>(p, a, o);
+	else if (type == SPHX_TESTPOINTS) testpoints_kernel<KERNEL, SA><<<grid, 128, 0, st>>>(p, a, o);
 	else if (type == SPHX_INTERFACE_DETECTION) interface_kernel<KERNEL><<<grid, 128, 0, st>>>(p, a, o);
-	else surface_kernel<KERNEL><<<grid, 128, 0, st>>>(p, a, o);
+	else surface_kernel<KERNEL, SA><<<grid, 128, 0, st>>>(p, a, o);
+}
+
+static int postprocess_run(sphx_ctx *ctx, int type,
+	void *vorticity, void *velInOut, void *infoInOut, void *normals, void *tke, void *eps,
+	const void *pos, const void *vel, const void *info, const uint32_t *hash,
+	const uint32_t *cellStart, const uint16_t *neibsList,
+	uint32_t particleRangeEnd, float cosconeanglefluid, float cosconeanglenonfluid, void *stream)
+{
+	SPHX_REQUIRE(ctx && ctx->have_params, "sphx_postprocess: constants not set");
+	SPHX_REQUIRE(type == SPHX_VORTICITY || type == SPHX_TESTPOINTS || type == SPHX_SURFACE_DETECTION || type == SPHX_INTERFACE_DETECTION,
+		"sphx_postprocess: non-existing postprocess filter invoked");
+	SPHX_REQUIRE(pos && hash && cellStart && neibsList, "sphx_postprocess: missing buffer (POS, HASH, CELLSTART, NEIBSLIST)");
+	const bool sa = ctx->dev.boundarytype == SPHX_SA_BOUNDARY;
+	if (!sa && ctx->dev.boundarytype != SPHX_DYN_BOUNDARY && ctx->dev.boundarytype != SPHX_LJ_BOUNDARY)
+		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx_postprocess: only LJ/DYN/SA boundaries are built");
+	// no reference problem has SA walls with two fluids: the interface kernel has no vertex section
+	if (sa && type == SPHX_INTERFACE_DETECTION)
+		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx_postprocess(INTERFACE_DETECTION): not built for SA_BOUNDARY (SURFACE_DETECTION is)");
+	if (!particleRangeEnd) return SPHX_OK;
+	FilterArgs a;
+	a.newVel = nullptr; a.pos = (const float4*)pos; a.vel = (const float4*)vel;
+	a.info = (const particleinfo*)info; a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList;
+	a.numParticles = particleRangeEnd;
+	PostArgs o;
+	o.vorticity = (float*)vorticity; o.velInOut = (float4*)velInOut; o.infoInOut = (particleinfo*)infoInOut;
+	o.normals = (float4*)normals; o.cosconeanglefluid = cosconeanglefluid; o.cosconeanglenonfluid = cosconeanglenonfluid;
+	o.tke = (float*)tke; o.eps = (float*)eps;
+	if (type == SPHX_VORTICITY) SPHX_REQUIRE(vorticity && vel && info, "sphx_postprocess(VORTICITY): needs VORTICITY, VEL, INFO");
+	if (type == SPHX_TESTPOINTS) SPHX_REQUIRE(velInOut && info, "sphx_postprocess(TESTPOINTS): needs VEL (updated in place), INFO");
+	if (type == SPHX_SURFACE_DETECTION || type == SPHX_INTERFACE_DETECTION) {
+		SPHX_REQUIRE(infoInOut && vel, "sphx_postprocess(SURFACE/INTERFACE_DETECTION): needs INFO (updated in place), VEL");
+		a.info = (const particleinfo*)infoInOut;
+	}
+	const dim3 grid(div_up_u(particleRangeEnd, 128));
+	hipStream_t st = (hipStream_t)stream;
+#define SPHX_POST_LAUNCH(K) do { if (sa) launch_post<K, true>(type, grid, st, ctx->dev, a, o); \
+		else launch_post<K, false>(type, grid, st, ctx->dev, a, o); } while (0)
+	switch (ctx->dev.kerneltype) {
+	case SPHX_CUBICSPLINE: SPHX_POST_LAUNCH(SPHX_CUBICSPLINE); break;
+	case SPHX_QUADRATIC:   SPHX_POST_LAUNCH(SPHX_QUADRATIC); break;
+	case SPHX_WENDLAND:    SPHX_POST_LAUNCH(SPHX_WENDLAND); break;
+	case SPHX_GAUSSIAN:    SPHX_POST_LAUNCH(SPHX_GAUSSIAN); break;
+	default: return sphx_set_error(SPHX_ERR_INVALID, "sphx_postprocess: invalid kernel type");
+	}
+#undef SPHX_POST_LAUNCH
+	SPHX_LAUNCH_CHECK("postprocess kernel");
+	return SPHX_OK;
 }
 
 extern "C" int sphx_postprocess(sphx_ctx *ctx, int type,
@@ -476,37 +543,22 @@ extern "C" int sphx_postprocess(sphx_ctx *ctx, int type,
 	uint32_t numParticles, uint32_t particleRangeEnd, float cosconeanglefluid, float cosconeanglenonfluid, void *stream)
 {
 	(void)numParticles;
-	SPHX_REQUIRE(ctx && ctx->have_params, "sphx_postprocess: constants not set");
-	SPHX_REQUIRE(type == SPHX_VORTICITY || type == SPHX_TESTPOINTS || type == SPHX_SURFACE_DETECTION || type == SPHX_INTERFACE_DETECTION,
-		"sphx_postprocess: non-existing postprocess filter invoked");
-	SPHX_REQUIRE(pos && hash && cellStart && neibsList, "sphx_postprocess: missing buffer (POS, HASH, CELLSTART, NEIBSLIST)");
-	if (ctx->dev.boundarytype != SPHX_DYN_BOUNDARY && ctx->dev.boundarytype != SPHX_LJ_BOUNDARY)
-		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx_postprocess: only LJ/DYN boundaries are built");
-	if (!particleRangeEnd) return SPHX_OK;
-	FilterArgs a;
-	a.newVel = nullptr; a.pos = (const float4*)pos; a.vel = (const float4*)vel;
-	a.info = (const particleinfo*)info; a.hash = hash; a.cellStart = cellStart; a.neibsList = neibsList;
-	a.numParticles = particleRangeEnd;
-	PostArgs o;
-	o.vorticity = (float*)vorticity; o.velInOut = (float4*)velInOut; o.infoInOut = (particleinfo*)infoInOut;
-	o.normals = (float4*)normals; o.cosconeanglefluid = cosconeanglefluid; o.cosconeanglenonfluid = cosconeanglenonfluid;
-	if (type == SPHX_VORTICITY) SPHX_REQUIRE(vorticity && vel && info, "sphx_postprocess(VORTICITY): needs VORTICITY, VEL, INFO");
-	if (type == SPHX_TESTPOINTS) SPHX_REQUIRE(velInOut && info, "sphx_postprocess(TESTPOINTS): needs VEL (updated in place), INFO");
-	if (type == SPHX_SURFACE_DETECTION || type == SPHX_INTERFACE_DETECTION) {
-		SPHX_REQUIRE(infoInOut && vel, "sphx_postprocess(SURFACE/INTERFACE_DETECTION): needs INFO (updated in place), VEL");
-		a.info = (const particleinfo*)infoInOut;
-	}
-	const dim3 grid(div_up_u(particleRangeEnd, 128));
-	hipStream_t st = (hipStream_t)stream;
-	switch (ctx->dev.kerneltype) {
-	case SPHX_CUBICSPLINE: launch_post<SPHX_CUBICSPLINE>(type, grid, st, ctx->dev, a, o); break;
-	case SPHX_QUADRATIC:   launch_post<SPHX_QUADRATIC>(type, grid, st, ctx->dev, a, o); break;
-	case SPHX_WENDLAND:    launch_post<SPHX_WENDLAND>(type, grid, st, ctx->dev, a, o); break;
-	case SPHX_GAUSSIAN:    launch_post<SPHX_GAUSSIAN>(type, grid, st, ctx->dev, a, o); break;
-	default: return sphx_set_error(SPHX_ERR_INVALID, "sphx_postprocess: invalid kernel type");
-	}
-	SPHX_LAUNCH_CHECK("postprocess kernel");
-	return SPHX_OK;
+	return postprocess_run(ctx, type, vorticity, velInOut, infoInOut, normals, nullptr, nullptr, pos, vel, info, hash, cellStart, neibsList,
+		particleRangeEnd, cosconeanglefluid, cosconeanglenonfluid, stream);
+}
+
+// TESTPOINTS of a k-epsilon run: BUFFER_TKE / BUFFER_EPSILON of the test points are written with the velocity (the reference does so
+// whenever the buffers exist); k-epsilon exists with SA_BOUNDARY only
+extern "C" int sphx_postprocess_testpoints_keps(sphx_ctx *ctx, void *velInOut, void *tke, void *eps,
+	const void *pos, const void *info, const uint32_t *hash, const uint32_t *cellStart, const uint16_t *neibsList,
+	uint32_t numParticles, uint32_t particleRangeEnd, void *stream)
+{
+	(void)numParticles;
+	SPHX_REQUIRE(ctx && ctx->have_params, "sphx_postprocess_testpoints_keps: constants not set");
+	SPHX_REQUIRE(ctx->dev.boundarytype == SPHX_SA_BOUNDARY, "sphx_postprocess_testpoints_keps: k-epsilon runs have SA_BOUNDARY");
+	SPHX_REQUIRE(tke && eps, "sphx_postprocess_testpoints_keps: needs TKE and EPSILON (updated in place)");
+	return postprocess_run(ctx, SPHX_TESTPOINTS, nullptr, velInOut, nullptr, nullptr, tke, eps, pos, nullptr, info, hash, cellStart, neibsList,
+		particleRangeEnd, 0.0f, 0.0f, stream);
 }
 
 // ==========================================================================================

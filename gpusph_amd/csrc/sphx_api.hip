@@ -1,5 +1,6 @@
 // sphx_api.hip -- context, constants and error plumbing of libsphx (C ABI in include/sphx.h).
 #include "sphx_internal.h"
+#include "gages.h"
 #include <cstdio>
 #include <cmath>
 #include <cstring>
@@ -120,6 +121,7 @@ extern "C" void sphx_destroy(sphx_ctx *ctx)
 	if (ctx->list_part_events) for (int k = 0; k < SPHX_LIST_PARTS_MAX; ++k) (void)hipEventDestroy(ctx->list_part[k]);
 	if (ctx->dem) (void)hipFree(ctx->dem);
 	if (ctx->open_rows) (void)hipFree(ctx->open_rows);
+	sphx_gage_scratch_release(ctx);
 	free_granular(ctx);
 	delete ctx->forces_events;
 	delete ctx;

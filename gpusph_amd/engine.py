@@ -97,7 +97,9 @@ class TimestepEngine(MultiGpuEngine):
         """POSTPROCESS command (src/GPUWorker.cc runCommand<POSTPROCESS>): VORTICITY returns a [n,3] tensor,
         TESTPOINTS updates the velocity rows of test points in place, SURFACE_DETECTION updates FG_SURFACE (and
         INTERFACE_DETECTION also FG_INTERFACE) in INFO in place, and returns the normals when asked; FLUX_COMPUTATION returns the
-        flux per open boundary, CALC_PRIVATE what the problem's calc_private makes of the state."""
+        flux per open boundary, CALC_PRIVATE what the problem's calc_private makes of the state.  With SA_BOUNDARY: VORTICITY,
+        TESTPOINTS (k and epsilon of the test points as well in a k-epsilon run) and SURFACE_DETECTION; INTERFACE_DETECTION raises
+        SphxUnsupported."""
         self._rows_for = None      # the velocity buffer may be rewritten behind torch's back (multigpu.py, _rows_for)
         if pptype == D.FLUX_COMPUTATION:
             return self.open_boundary_flux()
@@ -111,9 +113,15 @@ class TimestepEngine(MultiGpuEngine):
         detect = pptype in (D.SURFACE_DETECTION, D.INTERFACE_DETECTION)
         if detect and normals:
             nrm = out = torch.empty((self.alloc, 4), dtype=torch.float32, device=self.device)
+        if pptype == D.TESTPOINTS and self.keps:      # BUFFER_TKE / BUFFER_EPSILON of the test points are written with the velocity
+            self.k.postprocess_testpoints_keps(self.vel, self.ke["tke"], self.ke["eps"], self.pos, self.info, self.hash, self.cellStart,
+                                               self.neibslist, n)
+            return None
         self.k.postprocess(pptype, vort, self.vel if pptype == D.TESTPOINTS else None, self.info if detect else None, nrm,
                            self.pos, self.vel, self.info, self.hash, self.cellStart, self.neibslist, n,
                            getattr(pp, "cosconeanglefluid", 0.86), getattr(pp, "cosconeanglenonfluid", 0.5))
+        if detect:
+            self._surface_for = self._state_key()
         return None if out is None else out[:n]
 
     # ------------------------------------------------------------------ repacking run mode
@@ -150,6 +158,7 @@ class TimestepEngine(MultiGpuEngine):
         self.k.disable_free_surf_parts(self.pos, self.info, self.n)
         if self.iterations > 0:
             self.build_neibs()
+        self._surface_for = None
         if not reset:
             return
         # the restart below re-initialises velocities and densities only.  Option sets that carry more evolved state would need
@@ -256,6 +265,7 @@ class TimestepEngine(MultiGpuEngine):
         from . import hotfile
         if getattr(self, "granular", False):
             raise NotImplementedError("HotFile checkpoints of a run with the GRANULAR rheology are not built")
+        self._surface_for = None
         hf = hotfile.read_hotfile(path)
         a = hf["arrays"]
         n = hf["particles"]

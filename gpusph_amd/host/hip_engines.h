@@ -961,6 +961,9 @@ class HIPPostProcessEngine : public AbstractPostProcessEngine
 	mutable float m_cosf, m_cosn;   // PhysParams::cosconeangle{fluid,nonfluid}, read by setconstants
 
 	bool detects() const { return m_type == SURFACE_DETECTION || m_type == INTERFACE_DETECTION; }
+	// the framework has turbulence<KEPSILON>: BUFFER_TKE / BUFFER_EPSILON exist and TESTPOINTS updates them with the velocity
+	// (src/cuda/post_process.cu:153-154,176-178)
+	bool keps() const { return m_c->params().turbmodel == KEPSILON; }
 public:
 	HIPPostProcessEngine(HIPEngineContextPtr c, PostProcessType type, flag_t options) :
 		AbstractPostProcessEngine(options), m_c(c), m_type(type), m_cosf(0.86f), m_cosn(0.5f) {}
@@ -974,7 +977,7 @@ public:
 	flag_t get_written_buffers() const
 	{ return m_type == VORTICITY ? BUFFER_VORTICITY : detects() ? (m_options & BUFFER_NORMALS) : BUFFER_NONE; }
 	flag_t get_updated_buffers() const
-	{ return m_type == TESTPOINTS ? BUFFER_VEL : detects() ? BUFFER_INFO : BUFFER_NONE; }
+	{ return m_type == TESTPOINTS ? (keps() ? BUFFER_VEL | BUFFER_TKE | BUFFER_EPSILON : BUFFER_VEL) : detects() ? BUFFER_INFO : BUFFER_NONE; }
 
 	void process(const BufferList& bufread, BufferList& bufwrite, uint numParticles, uint particleRangeEnd,
 		uint, const GlobalData * const)
@@ -984,6 +987,12 @@ public:
 		// (src/cuda/post_process.cu:175-177,252-254; INFO is shared between states, hence MULTISTATE_SAFE)
 		float4 *velInOut = m_type == TESTPOINTS ? bufwrite.getData<BUFFER_VEL>() : NULL;
 		particleinfo *infoInOut = detects() ? bufwrite.getData<BUFFER_INFO, BufferList::MULTISTATE_SAFE>() : NULL;
+		if (m_type == TESTPOINTS && keps()) {
+			sphx_throw(sphx_postprocess_testpoints_keps(m_c->ctx(), velInOut, bufwrite.getData<BUFFER_TKE>(), bufwrite.getData<BUFFER_EPSILON>(),
+				bufread.getData<BUFFER_POS>(), bufread.getData<BUFFER_INFO>(), bufread.getData<BUFFER_HASH>(),
+				bufread.getData<BUFFER_CELLSTART>(), bufread.getData<BUFFER_NEIBSLIST>(), numParticles, particleRangeEnd, NULL));
+			return;
+		}
 		sphx_throw(sphx_postprocess(m_c->ctx(), (int)m_type,
 			m_type == VORTICITY ? bufwrite.getData<BUFFER_VORTICITY>() : NULL,
 			velInOut, infoInOut,

@@ -441,6 +441,22 @@ class HipKernels:
                                              p(pos), p(vel), p(info), p(hash_), p(cellStart), p(neibslist), n, n,
                                              float(cosf), float(cosn), self._s()))
 
+    def postprocess_testpoints_keps(self, vel_inout, tke, eps, pos, info, hash_, cellStart, neibslist, n):
+        """TESTPOINTS of a k-epsilon run: the velocity, k and epsilon rows of the test points, in place"""
+        p = capi.ptr
+        capi.check(self.lib.sphx_postprocess_testpoints_keps(self.ctx.handle, p(vel_inout), p(tke), p(eps), p(pos), p(info), p(hash_),
+                                                             p(cellStart), p(neibslist), n, n, self._s()))
+
+    # ---- wave gages (gages.hip): partials per gage over rows [0, n), and the levels of (combined) partials
+    def wave_gages(self, partials, gages, num_gages, pos, info, hash_, n):
+        p = capi.ptr
+        capi.check(self.lib.sphx_wave_gages(self.ctx.handle, p(partials), p(gages), int(num_gages), p(pos), p(info), p(hash_), int(n),
+                                            self._s()))
+
+    def wave_gages_finish(self, z, partials, gages, num_gages):
+        p = capi.ptr
+        capi.check(self.lib.sphx_wave_gages_finish(self.ctx.handle, p(z), p(partials), p(gages), int(num_gages), self._s()))
+
     # ---- SA open boundaries (ENABLE_INLET_OUTLET): the passes of gpusph_amd/csrc/sa_io.hip behind the driver sequence of
     # gpusph_amd.multigpu (_sa_post_euler_io).  The first five entry points are verified on the GPU; the condition passes, the
     # density summation, the forces, the diffusion and the water depth have run over their own source on the CPU only

@@ -116,6 +116,7 @@ class MultiGpuEngine:
         # it.  _rows_for = (the tensor the last Euler step wrote, its torch version counter): anything that rewrites it through
         # torch bumps the counter, the library's own rewrites (sort, filters, halo import) go to the other buffer or clear this
         self._rows_for = None
+        self._surface_for = None      # the state (_state_key) whose FG_SURFACE flags are in INFO: wave_gages runs the detection otherwise
         self._rows_follow = (not self.sa and not self.grenier and not self.effvisc_on and hasattr(kernels, "eos_rows_follow_euler")
                              and problem.simparams.sph_formulation in (D.SPH_F1, D.SPH_F2))
         if self._rows_follow:
@@ -846,6 +847,66 @@ class MultiGpuEngine:
             self.transport.allreduce_sum(tot)
         tot = tot.cpu().numpy()
         return tot[:3].astype(np.float32), tot[3:].astype(np.float32)
+
+    # ------------------------------------------------------------------ wave gages
+    def _state_key(self):
+        return (self.iterations, self.pos.data_ptr(), self.info.data_ptr(), self.n_int)
+
+    def detect_surface(self, normals=None):
+        """SURFACE_DETECTION of the rows this rank owns (their lists reach into the halo): FG_SURFACE in INFO, in place"""
+        pp = self.problem.physparams
+        self.k.postprocess(D.SURFACE_DETECTION, None, None, self.info, normals, self.pos, self.vel, self.info, self.hash, self.cellStart,
+                           self.neibslist, self.n_int, getattr(pp, "cosconeanglefluid", 0.86), getattr(pp, "cosconeanglenonfluid", 0.5))
+        self._surface_for = self._state_key()
+
+    def wave_gages(self, gages=None):
+        """The water level at the problem's gages (Problem.add_gage), or at `gages` ((n, 4): x, y, unused, smoothing length): float64
+        [n], computed on the device from the free-surface particles (GPUSPH::doWrite, src/GPUSPH.cc:1579-1697, without its host
+        copy of the state).  The surface detection runs first if it has not run on this state (the reference force-enables it for
+        a problem with gages, src/ProblemCore.cc:102).  Every rank counts the rows it owns, never its halo, and the ranks combine
+        their partial sums (smoothing length > 0) or take the nearest particle of all (0; the lower rank among equals).
+        NaN where a smoothed gage has no surface particle in reach, 0 where a nearest-mode gage has none at all.  Needs the neighbour
+        list of the state (build_neibs, or a step).  Synchronises."""
+        g = np.ascontiguousarray(self.problem.gages if gages is None else gages, dtype=np.float64).reshape(-1, 4)
+        ng = len(g)
+        if self._surface_for != self._state_key():
+            self.detect_surface()
+        dev = self.device
+        d_g = torch.from_numpy(g).to(dev)
+        part = torch.zeros((max(ng, 1), 4), dtype=torch.float64, device=dev)
+        self.k.wave_gages(part, d_g, ng, self.pos, self.info, self.hash, self.n_int)
+        if not ng:
+            return np.zeros(0, dtype=np.float64)
+        if self.world > 1:
+            nearest = np.nonzero(~(g[:, 3] > 0))[0]
+            mine = part.cpu().numpy()
+            sums = part[:, :2].contiguous()
+            self.transport.allreduce_sum(sums)
+            part[:, :2] = sums
+            for k in nearest:       # the smallest r of all ranks: (bits of r >= 0, bits of z), +inf where a rank has none
+                r = mine[k, 1] if mine[k, 2] else np.inf
+                got = self.transport.allgather_pair(int(np.float64(r).view(np.uint64)), int(np.float64(mine[k, 0]).view(np.uint64)), dev)
+                rb, zb = min(got, key=lambda v: v[0])          # (min returns the first of equals: the lowest rank)
+                rr = float(np.uint64(rb).view(np.float64))
+                part[k] = torch.tensor([float(np.uint64(zb).view(np.float64)) if np.isfinite(rr) else 0.0, rr,
+                                        1.0 if np.isfinite(rr) else 0.0, 0.0], dtype=torch.float64, device=dev)
+        z = torch.empty(ng, dtype=torch.float64, device=dev)
+        self.k.wave_gages_finish(z, part, d_g, ng)
+        return z.cpu().numpy()
+
+    def write_wave_gages(self, path, gages=None):
+        """one line of WaveGage.txt (CommonWriter::write_WaveGage, src/writers/CommonWriter.cc:244-252) for the current state;
+        the header (:72-80) goes first into a new file.  Every rank takes part in the reading, rank 0 writes.  Returns the levels."""
+        from . import commonwriter
+        z = self.wave_gages(gages)
+        if self.rank != 0:
+            return z
+        new = not os.path.exists(path) or os.path.getsize(path) == 0
+        with open(path, "a") as f:
+            if new:
+                f.write(commonwriter.wave_gage_header(len(z)))
+            f.write(commonwriter.wave_gage_line(self.time(), z))
+        return z
 
     def download_internal(self):
         n = self.n_int

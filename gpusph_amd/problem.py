@@ -77,6 +77,14 @@ class Problem:
         self.planes = []            # [(unit normal (3), reference point (3), global coordinates)], PlaneList
         self.moving_bodies_callback = None   # ProblemCore::moving_bodies_callback: f(index, t0, t1, initial_kdata, kdata) -> (dx, dr)
         self.m_maxFall = float("nan")        # ProblemAPI<1>::setMaxFall
+        self.gages = []                      # SimParams::gage (GageList): [x, y, z (output), smoothing length]
+
+    def add_gage(self, x, y, slength=0.0):
+        """ProblemCore::add_gage (src/ProblemCore.cc:939-942): a wave gage at (x, y) in global coordinates.  slength > 0: the level is
+        the Wendland-weighted mean z of the free-surface particles within 2 slength; 0: the z of the nearest one."""
+        if slength < 0:
+            raise ValueError("the smoothing length of a gage is >= 0")
+        self.gages.append([float(x), float(y), 0.0, float(slength)])
 
     def plane_tables(self):
         """plane_t arrays as ProblemCore::copy_planes hands them to setplanes: unit normal, grid cell and
@@ -1021,6 +1029,39 @@ class SABox(Problem):
         a = super().copy_to_array()
         a.update(vertices=self.vertices.copy(), boundelements=self.boundelements.copy(), gradgamma=self.gradgamma.copy())
         return a
+
+
+class SAProbeBox(SABox):
+    """SABox with what Spheric2SA is run for (src/problems/Spheric2SA.cu:58-59,92-105): pressure probes (test points, PT_TESTPOINT rows
+    behind the tank's particles, with ids of their own) and wave gages.  testpoints: (n, 3) global positions inside the domain (the
+    tank plus two deltap on every side); gages: (x, y) or (x, y, smoothing length) each.  Test points are nobody's neighbours: the run
+    of the tank's particles is that of the SABox with the same arguments."""
+
+    def __init__(self, deltap=0.05, *, testpoints=(), gages=(), **kw):
+        super().__init__(deltap, **kw)
+        self.m_name = "SAProbeBox"
+        tp = np.asarray(testpoints, dtype=np.float64).reshape(-1, 3)
+        lo, hi = self.m_origin, self.m_origin + self.m_size
+        if ((tp < lo) | (tp >= hi)).any():
+            raise ValueError("a test point lies outside the domain %s .. %s" % (lo, hi))
+        self.testpoints = tp
+        nt, n0 = len(tp), len(self.parts.info)
+        if nt:
+            pos = np.empty((nt, 4), dtype=np.float64)
+            pos[:, :3] = tp
+            pos[:, 3] = self.physparams.rho0[0] * self.m_deltap ** 3
+            vel = np.zeros((nt, 4), dtype=np.float32)
+            vel[:, 3] = self.initial_density(pos)
+            info = make_particleinfo(np.full(nt, D.PT_TESTPOINT, dtype=np.uint16), np.zeros(nt, dtype=np.uint16),
+                                     np.arange(n0, n0 + nt, dtype=np.uint32))
+            self.parts = HostParticles(np.concatenate([self.parts.pos_global, pos]), np.concatenate([self.parts.vel, vel]),
+                                       np.concatenate([self.parts.info, info]))
+            self.vertices = np.concatenate([self.vertices, np.zeros((nt, 4), dtype=np.uint32)])
+            self.boundelements = np.concatenate([self.boundelements, np.full((nt, 4), np.nan, dtype=np.float32)])
+            self.gradgamma = np.concatenate([self.gradgamma, np.full((nt, 4), np.nan, dtype=np.float32)])
+        self.num_testpoints = nt
+        for g in gages:
+            self.add_gage(*g)
 
 
 class SALoadBox(SABox):

@@ -561,12 +561,42 @@ int sphx_filter_process(sphx_ctx *ctx, int filtertype, void *newVel,
  *                           BUFFER_NORMALS option) may be NULL; cosconeangle*: PhysParams, src/physparams.h:370-371
  *   SPHX_INTERFACE_DETECTION  multi-fluid runs (calcInterfaceparticleDevice, post_process_kernel.cu:388-560): FG_SURFACE as
  *                           above plus FG_INTERFACE for fluid particles whose same-fluid cone is empty; same buffers
- * Buffers a type does not use may be NULL. */
+ * Buffers a type does not use may be NULL.
+ * Boundary types: LJ / DYN / MK contexts run the kernels above as they are.  A context with SA_BOUNDARY runs instantiations of
+ * its own: TESTPOINTS also sums over the vertex section of the test point's list (vertex particles carry mass, density and
+ * velocity; calcTestpointsVelocityDevice<SA_BOUNDARY>), SURFACE_DETECTION walks the fluid, boundary and vertex sections
+ * (for_every_neib<SA_BOUNDARY>, src/cuda/neibs_iteration.cuh:341-360), VORTICITY is the same kernel (fluid neighbours only).
+ * SPHX_INTERFACE_DETECTION with SA_BOUNDARY is SPHX_ERR_UNSUPPORTED (no reference problem has SA walls and two fluids). */
 int sphx_postprocess(sphx_ctx *ctx, int type,
 	void *vorticity, void *velInOut, void *infoInOut, void *normals,
 	const void *pos, const void *vel, const void *info, const uint32_t *hash,
 	const uint32_t *cellStart, const uint16_t *neibsList,
 	uint32_t numParticles, uint32_t particleRangeEnd, float cosconeanglefluid, float cosconeanglenonfluid, void *stream);
+
+/* SPHX_TESTPOINTS of a k-epsilon run (SA_BOUNDARY): as above, and BUFFER_TKE / BUFFER_EPSILON of the test points are overwritten in
+ * place with the average of k and epsilon over the same neighbours with the same weights (zeros where nothing is in reach), which
+ * the reference does whenever the buffers exist (post_process_kernel.cu:206-213,222-239).  The velocity rows are those of
+ * sphx_postprocess(SPHX_TESTPOINTS), bit for bit. */
+int sphx_postprocess_testpoints_keps(sphx_ctx *ctx, void *velInOut, void *tke, void *eps,
+	const void *pos, const void *info, const uint32_t *hash, const uint32_t *cellStart, const uint16_t *neibsList,
+	uint32_t numParticles, uint32_t particleRangeEnd, void *stream);
+
+/* ---- wave gages (GPUSPH::doWrite, src/GPUSPH.cc:1565-1571,1649-1668,1688-1694) ------------------ */
+/* The water level at up to SPHX_MAX_GAGES points from the ACTIVE particles with FG_SURFACE among rows [0, numParticles): run
+ * SPHX_SURFACE_DETECTION on the state first (the reference force-enables it for a problem with gages, src/ProblemCore.cc:102).
+ * gages: device, numGages x 4 doubles (x, y, unused, smoothing length h) in global coordinates.  Double precision on the global
+ * position (cell size)*(cell + 1/2) + local position + world origin (calcGlobalPosOffset, src/GlobalData.h:378-384), cell size and
+ * world origin as uploaded by sphx_set_constants.
+ *   h > 0   d_partials[4 g ..] = (sum z W, sum W, 0, 0) over r_xy < 2 h, W = Wendland2D(r_xy, h)
+ *   h = 0   d_partials[4 g ..] = (z, r_xy, found, row) of the particle with the smallest r_xy, the lowest row among equals
+ * Deterministic: no floating-point atomics, the same state gives the same bits whatever the device.  Partials, not levels, so
+ * that several ranks can combine theirs (sums: sphx_halo_allreduce_sum_f64; nearest: the smallest r, sphx_halo_allgather_u64x2)
+ * before sphx_wave_gages_finish turns them into d_z[numGages]: sum z W / sum W (NaN over dry ground: 0/0, as the reference), or
+ * the nearest particle's z (0 when there is no surface particle at all).  More than SPHX_MAX_GAGES gages: SPHX_ERR_INVALID. */
+#define SPHX_MAX_GAGES 64
+int sphx_wave_gages(sphx_ctx *ctx, double *d_partials, const double *gages, uint32_t numGages,
+	const void *pos, const void *info, const uint32_t *hash, uint32_t numParticles, void *stream);
+int sphx_wave_gages_finish(sphx_ctx *ctx, double *d_z, const double *d_partials, const double *gages, uint32_t numGages, void *stream);
 
 /* ---- AbstractIntegrationEngine ------------------------------------------------------------ */
 /* basicstep (src/cuda/euler.cu:329-366).  dt is the step's dt or dt/2 exactly as the
