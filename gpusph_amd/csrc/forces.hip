@@ -2130,8 +2130,7 @@ tile_lists_kernel(DevParams p, const neibdata *__restrict__ list, const uint32_t
 	uint32_t *__restrict__ tiles, uint32_t *tileCtl, uint32_t *__restrict__ tileRows, uint32_t *__restrict__ tileRuns,
 	uint2 *__restrict__ tileList, uint32_t listCapBatches, uint32_t *__restrict__ laneRec, uint32_t *__restrict__ laneIndex,
 	uint32_t laneCap, int saVertex /* SA_BOUNDARY lists: the second section is the VERTEX section */,
-	uint32_t shareLo /* tile_share_start */,
-	uint32_t homeFrom, uint32_t homeTo /* only the tiles whose last home particle lies in [homeFrom, homeTo): a build in parts */)
+	uint32_t shareLo /* tile_share_start */)
 {
 	__shared__ uint32_t sCellRel[TILE_WROWS*TILE_KW], sCellBase[TILE_WROWS*TILE_KW], sCellStart[TILE_WROWS*TILE_KW];
 	__shared__ uint32_t sRowTotal[TILE_WROWS], sRowStart[TILE_WROWS], sRowContig[TILE_WROWS], sRowBase[TILE_WROWS];
@@ -2200,17 +2199,6 @@ tile_lists_kernel(DevParams p, const neibdata *__restrict__ list, const uint32_t
 		const int ca = __builtin_amdgcn_readlane((int)d, 2), dnc = __builtin_amdgcn_readlane((int)d, 3);
 		const uint32_t P = (uint32_t)(__builtin_amdgcn_readlane((int)d, 8) + __builtin_amdgcn_readlane((int)d, 9) +
 			__builtin_amdgcn_readlane((int)d, 10) + __builtin_amdgcn_readlane((int)d, 11));        // home particles (<= TILE_PMAX)
-		{	// a build in parts: the tile belongs to the part that holds its last home particle (its lists are all there then); every
-			// thread of the workgroup sees the same descriptor, so all of them skip or none
-			uint32_t homeEnd = 0u;
-#pragma unroll
-			for (int r = 0; r < TILE_HROWS; ++r) {
-				const uint32_t first = (uint32_t)__builtin_amdgcn_readlane((int)d, 4 + r), cnt = (uint32_t)__builtin_amdgcn_readlane((int)d, 8 + r);
-				if (cnt) homeEnd = max(homeEnd, first + cnt);
-			}
-			const uint32_t last = homeEnd ? homeEnd - 1u : 0u;
-			if (last < homeFrom || last >= homeTo) continue;
-		}
 		const uint32_t C = (P + 63u)/64u;
 		const uint32_t preCnt = pre.cnt, preHash = pre.hash;
 		const particleinfo preInfo = pre.info;
@@ -2500,8 +2488,7 @@ tile_lists_kernel(DevParams p, const neibdata *__restrict__ list, const uint32_t
 	}
 }
 
-int sphx_tile_lists_launch(sphx_ctx *ctx, const uint16_t *neibsList, const void *info, const uint32_t *hash, const uint32_t *cellStart, bool sa, hipStream_t st,
-	uint32_t homeFrom, uint32_t homeTo)
+int sphx_tile_lists_launch(sphx_ctx *ctx, const uint16_t *neibsList, const void *info, const uint32_t *hash, const uint32_t *cellStart, bool sa, hipStream_t st)
 {
 	if (!ctx->tile_list || !ctx->tile_runs || !ctx->tile_rows || !ctx->tile_lane_rec || !ctx->tile_lane_index || !ctx->neib_counts) {
 		sphx_tiles_invalidate(ctx);
@@ -2512,7 +2499,7 @@ int sphx_tile_lists_launch(sphx_ctx *ctx, const uint16_t *neibsList, const void 
 	const bool plain = !sa && ctx->dev.turbmodel == SPHX_ARTIFICIAL && ctx->dev.numfluids == 1 && ctx->dev.boundarytype == SPHX_DYN_BOUNDARY;
 	tile_lists_kernel<<<grid, TL_THREADS, 0, st>>>(ctx->dev, neibsList, ctx->neib_counts, (const particleinfo*)info, hash, cellStart, ctx->cell_end_copy,
 		ctx->tiles, ctx->tile_ctl, ctx->tile_rows, ctx->tile_runs, ctx->tile_list, ctx->tile_list_batches, ctx->tile_lane_rec, ctx->tile_lane_index,
-		ctx->tile_lane_cap, sa ? 1 : 0, plain ? TILE_SHARE_LO_PLAIN : 32u, homeFrom, homeTo);
+		ctx->tile_lane_cap, sa ? 1 : 0, plain ? TILE_SHARE_LO_PLAIN : 32u);
 	SPHX_LAUNCH_CHECK("tile_lists_kernel");
 	return SPHX_OK;
 }

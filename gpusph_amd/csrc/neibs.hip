@@ -758,10 +758,7 @@ struct SideJoin {
 static hipStream_t sphx_side_stream(sphx_ctx *ctx)
 {
 	if (ctx->side_stream || ctx->tiling_inline) return ctx->side_stream;
-	int prLeast = 0, prGreatest = 0;
-	if (ctx->side_priority) (void)hipDeviceGetStreamPriorityRange(&prLeast, &prGreatest);
-	if ((ctx->side_priority ? hipStreamCreateWithPriority(&ctx->side_stream, hipStreamNonBlocking, prGreatest)
-	                        : hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking)) != hipSuccess) { (void)hipGetLastError(); ctx->side_stream = nullptr; }
+	if (hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ctx->side_stream = nullptr; }
 	else if (hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming) != hipSuccess ||
 	         hipEventCreateWithFlags(&ctx->side_join, hipEventDisableTiming) != hipSuccess) {
 		(void)hipGetLastError(); (void)hipStreamDestroy(ctx->side_stream); ctx->side_stream = nullptr;
@@ -806,46 +803,6 @@ static int tiling_launch(sphx_ctx *ctx, const NeibsBuild &b, SideJoin &join)
 	ctx->tiles_built = true;
 	ctx->tiles_cellstart = b.cellStart;
 	ctx->tiles_neibslist = b.neibsList;
-	return SPHX_OK;
-}
-
-// The list build.  In one launch, or, of a build whose tiling is on the side stream, in parts: tile_lists_kernel is a chain of
-// dependent round trips per tile at ten waves per CU (forces.hip): it needs little of the vector units and leaves most of the CU
-// idle; build_neibs_kernel is bound by vector issue.  So the list is built in `list_parts` launches over consecutive particle
-// ranges, and the tile lists of the tiles whose home particles are all listed go to the side stream behind each of them: they
-// run beside the list build of the next part, and only the last part's tile lists are left over at the end.  Lists, counters and
-// tile lists are what one launch each gives (the tiles get their room in the list stream in another order, which nothing reads).
-// *inParts: the tile lists have been launched here (and the side stream's join is recorded behind them)
-static int list_build(sphx_ctx *ctx, const NeibsBuild &b, bool tiling_on_side, bool *inParts)
-{
-	const auto launch = [&](uint32_t from, uint32_t to) {      // neibs_build.hip
-		return sphx_neibs_list_launch_part(ctx, b.neibsList, b.pos, b.info, b.hash, b.cellStart, b.cellEnd, b.vertices, b.boundElements,
-			b.vertPos0, b.vertPos1, b.vertPos2, b.numParticles, from, to, b.sqinfluenceradius, b.boundNlSqInflRad, b.st); };
-	int parts = 1;
-	if (tiling_on_side && ctx->list_parts > 1 && b.particleRangeEnd >= 65536u*(uint32_t)ctx->list_parts) {
-		if (!ctx->list_part_events) {
-			int made = 0;
-			for (; made < SPHX_LIST_PARTS_MAX; ++made)
-				if (hipEventCreateWithFlags(&ctx->list_part[made], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); break; }
-			if (made == SPHX_LIST_PARTS_MAX) ctx->list_part_events = true;
-			else for (int k = 0; k < made; ++k) (void)hipEventDestroy(ctx->list_part[k]);
-		}
-		if (ctx->list_part_events) parts = ctx->list_parts;
-	}
-	*inParts = parts > 1;
-	if (parts == 1) return launch(0u, b.particleRangeEnd);
-	const uint32_t per = div_up_u(div_up_u(b.particleRangeEnd, (uint32_t)parts), 1024u)*1024u;      // whole workgroups of the list build
-	for (int k = 0; k < parts; ++k) {
-		const uint32_t from = (uint32_t)k*per, to = (k == parts - 1) ? b.particleRangeEnd : min(b.particleRangeEnd, from + per);
-		if (from >= b.particleRangeEnd) break;
-		int rc = launch(from, to);
-		if (rc != SPHX_OK) return rc;
-		SPHX_HIP(hipEventRecord(ctx->list_part[k], b.st));
-		SPHX_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->list_part[k], 0));
-		rc = sphx_tile_lists_launch(ctx, b.neibsList, b.info, b.hash, b.cellStart, b.sa, ctx->side_stream, from, (k == parts - 1) ? 0xFFFFFFFFu : to);
-		if (rc != SPHX_OK) return rc;
-	}
-	SPHX_HIP(hipEventRecord(ctx->side_join, ctx->side_stream));
 	return SPHX_OK;
 }
 
@@ -916,15 +873,13 @@ static int sa_row_lists(sphx_ctx *ctx, const NeibsBuild &b)
 	return SPHX_OK;
 }
 
-// the lists of the tiled particles in the form the tiled forces kernel walks (forces.hip), unless the build in parts has made
-// them.  Then the tiling's overflow flag travels to the host behind the build, without a synchronisation: the forces passes
-// that find it arrived (sphx_tiles_current) launch exactly one kernel, the others keep the guarded stand-by
-static int tile_lists_and_overflow_copy(sphx_ctx *ctx, const NeibsBuild &b, bool listsMade)
+// the lists of the tiled particles in the form the tiled forces kernel walks (forces.hip).  Then the tiling's overflow flag travels
+// to the host behind the build, without a synchronisation: the forces passes that find it arrived (sphx_tiles_current) launch
+// exactly one kernel, the others keep the guarded stand-by
+static int tile_lists_and_overflow_copy(sphx_ctx *ctx, const NeibsBuild &b)
 {
-	if (!listsMade) {
-		const int rc = sphx_tile_lists_launch(ctx, b.neibsList, b.info, b.hash, b.cellStart, b.sa, b.st);
-		if (rc != SPHX_OK) return rc;
-	}
+	const int rc = sphx_tile_lists_launch(ctx, b.neibsList, b.info, b.hash, b.cellStart, b.sa, b.st);
+	if (rc != SPHX_OK) return rc;
 	if (!ctx->tiles_built || !ctx->ovf_host) return SPHX_OK;      // (no room for the tile lists: no tiling after all)
 	SPHX_HIP(hipMemcpyAsync(ctx->ovf_host, ctx->tile_ctl, 2*sizeof(uint32_t), hipMemcpyDeviceToHost, b.st));
 	SPHX_HIP(hipEventRecord(ctx->ovf_event, b.st));
@@ -965,18 +920,18 @@ extern "C" int sphx_build_neibs_sa(sphx_ctx *ctx, uint16_t *neibsList, void *ver
 		if (rc == SPHX_OK && ctx->tile_list) rc = tiling_launch(ctx, b, sideJoin);
 		if (rc != SPHX_OK) return rc;
 	}
-	bool tileListsMade = false;
-	rc = list_build(ctx, b, sideJoin.armed, &tileListsMade);
+	rc = sphx_neibs_list_launch(ctx, b.neibsList, b.pos, b.info, b.hash, b.cellStart, b.cellEnd, b.vertices, b.boundElements,
+		b.vertPos0, b.vertPos1, b.vertPos2, b.numParticles, b.particleRangeEnd, b.sqinfluenceradius, b.boundNlSqInflRad, b.st);      // neibs_build.hip
 	if (rc != SPHX_OK) return rc;
 	neibs_counters_fold_kernel<<<1, NEIBS_SPREAD, 0, st>>>(ctx->counters_dev);
 	SPHX_LAUNCH_CHECK("neibs_counters_fold_kernel");
-	if (sideJoin.armed) {      // the tiling (and, of a build in parts, the tile lists) is there for everything queued from here on
+	if (sideJoin.armed) {      // the tiling is there for everything queued from here on
 		SPHX_HIP(hipStreamWaitEvent(st, ctx->side_join, 0));
 		sideJoin.armed = false;
 	}
 	rc = sa_row_lists(ctx, b);
 	if (rc != SPHX_OK) return rc;
-	return ctx->tiles_built ? tile_lists_and_overflow_copy(ctx, b, tileListsMade) : SPHX_OK;
+	return ctx->tiles_built ? tile_lists_and_overflow_copy(ctx, b) : SPHX_OK;
 }
 
 extern "C" int sphx_neibs_resetinfo(sphx_ctx *ctx, void *stream)

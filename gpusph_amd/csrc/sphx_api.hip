@@ -47,21 +47,14 @@ extern "C" int sphx_create(sphx_ctx **out, int device)
 	// The switches of the environment, all read here: they hold for this context from its creation on.
 	//   SPHX_DISABLE_TILES=1   always the generic gather kernels, no tiling is built (A/B runs, tests)
 	//   SPHX_NEIBS_MFMA=1      the list build's prepass on the matrix cores (neibs_build.hip: bit-identical, measured slower)
-	//   SPHX_LIST_PARTS=n      a tiled list build in n parts, the tile lists of a part beside the list build of the next one
-	//                          (sphx_build_neibs_sa); 1 = one launch each
 	//   SPHX_TILING_INLINE     (set to anything) the tiling of a build on the caller's stream instead of the side stream (A/B)
-	//   SPHX_SIDE_PRIORITY     (set to anything) the side stream at the highest priority, so that the dispatcher prefers its
-	//                          workgroups whenever room comes free on a CU (experiment)
 	//   SPHX_TILE_DEBUG        (ForcesArgs::dbg: timing experiments, some of which skip work and give wrong results) only exists in
 	//                          a library built with -DSPHX_TILE_DEBUG_BUILD (make EXTRA=-DSPHX_TILE_DEBUG_BUILD); the product
 	//                          library ignores the variable
 	const auto is1 = [](const char *name) { const char *v = getenv(name); return v && v[0] == '1'; };
 	ctx->disable_tiles = is1("SPHX_DISABLE_TILES");
 	ctx->neibs_mfma = is1("SPHX_NEIBS_MFMA");
-	{ const char *lp = getenv("SPHX_LIST_PARTS"); const int n = lp ? atoi(lp) : SPHX_LIST_PARTS_DEFAULT;
-	  ctx->list_parts = n < 1 ? 1 : n > SPHX_LIST_PARTS_MAX ? SPHX_LIST_PARTS_MAX : n; }
 	ctx->tiling_inline = getenv("SPHX_TILING_INLINE") != nullptr;
-	ctx->side_priority = getenv("SPHX_SIDE_PRIORITY") != nullptr;
 	ctx->tile_debug = 0;
 #ifdef SPHX_TILE_DEBUG_BUILD
 	const char *dbg = getenv("SPHX_TILE_DEBUG");
@@ -118,7 +111,6 @@ extern "C" void sphx_destroy(sphx_ctx *ctx)
 	if (ctx->tile_ctl) (void)hipFree(ctx->tile_ctl);
 	if (ctx->ovf_host) { (void)hipHostFree(ctx->ovf_host); (void)hipEventDestroy(ctx->ovf_event); }
 	if (ctx->side_stream) { (void)hipStreamDestroy(ctx->side_stream); (void)hipEventDestroy(ctx->side_fork); (void)hipEventDestroy(ctx->side_join); }
-	if (ctx->list_part_events) for (int k = 0; k < SPHX_LIST_PARTS_MAX; ++k) (void)hipEventDestroy(ctx->list_part[k]);
 	if (ctx->dem) (void)hipFree(ctx->dem);
 	if (ctx->open_rows) (void)hipFree(ctx->open_rows);
 	sphx_gage_scratch_release(ctx);

@@ -140,8 +140,6 @@ struct NeibsCounters {   // device counters of cuneibs (src/cuda/buildneibs_kern
 #define NEIBS_SPREAD 256
 struct NeibsSpread { int maxFluidBoundaryNeibs, maxVertexNeibs; unsigned long long numInteractions; };
 
-#define SPHX_LIST_PARTS_MAX 16
-#define SPHX_LIST_PARTS_DEFAULT 1
 // GRANULAR: what sphx_set_granular holds (it outlives a new sphx_set_constants, like the planes), and the scratch of
 // sphx_jacobi_solve (granular.hip): the compact rows that iterate and their stored list entries, column-major
 struct GranularState {
@@ -218,14 +216,9 @@ struct sphx_ctx {
 	// on a stream of the context's own next to build_neibs_kernel, forked from and joined to the caller's stream by events
 	hipStream_t side_stream;
 	hipEvent_t  side_fork, side_join;
-	// a tiled build in parts (sphx_build_neibs_sa): the lists of part k are there
-	hipEvent_t  list_part[SPHX_LIST_PARTS_MAX];
-	int         list_parts;    // parts of a tiled list build (SPHX_LIST_PARTS in the environment when the context was created)
-	bool        list_part_events;
 	bool        ovf_pending;
 	bool        disable_tiles; // SPHX_DISABLE_TILES=1 in the environment (A/B testing)
 	bool        tiling_inline; // SPHX_TILING_INLINE set in the environment when the context was created: no side stream
-	bool        side_priority; // SPHX_SIDE_PRIORITY set ...: the side stream at the highest priority
 	bool        neibs_mfma;    // SPHX_NEIBS_MFMA=1 in the environment when the context was created: the list build's prepass on the matrix cores (neibs_build.hip)
 	int         tile_debug;    // SPHX_TILE_DEBUG (timing experiments; only with -DSPHX_TILE_DEBUG_BUILD)
 	unsigned long long *tile_prof;   // ... & 16: phase timers of the tiled forces kernel
@@ -353,13 +346,8 @@ int sphx_neibs_list_launch(sphx_ctx *ctx, uint16_t *neibsList, const void *pos, 
 	const uint32_t *cellStart, const uint32_t *cellEnd, const void *vertices, const void *boundElements,
 	void *vertPos0, void *vertPos1, void *vertPos2, uint32_t numParticles, uint32_t particleRangeEnd,
 	float sqinfluenceradius, float boundNlSqInflRad, hipStream_t st);   // neibs_build.hip: the whole list (the host emulation of the tests calls it)
-int sphx_neibs_list_launch_part(sphx_ctx *ctx, uint16_t *neibsList, const void *pos, const void *info, const uint32_t *hash,
-	const uint32_t *cellStart, const uint32_t *cellEnd, const void *vertices, const void *boundElements,
-	void *vertPos0, void *vertPos1, void *vertPos2, uint32_t numParticles, uint32_t firstParticle, uint32_t particleRangeEnd,
-	float sqinfluenceradius, float boundNlSqInflRad, hipStream_t st);   // ... of [firstParticle, particleRangeEnd)
-// the tile lists of the tiles whose LAST home particle lies in [homeFrom, homeTo) (the whole tiling: 0, 0xFFFFFFFF)
-int sphx_tile_lists_launch(sphx_ctx *ctx, const uint16_t *neibsList, const void *info, const uint32_t *hash, const uint32_t *cellStart, bool sa, hipStream_t st,
-	uint32_t homeFrom = 0u, uint32_t homeTo = 0xFFFFFFFFu);
+// the tile lists of the whole tiling (forces.hip)
+int sphx_tile_lists_launch(sphx_ctx *ctx, const uint16_t *neibsList, const void *info, const uint32_t *hash, const uint32_t *cellStart, bool sa, hipStream_t st);
 // SA_BOUNDARY engines over the tiles (forces.hip): mode = SPHX_SA_TILE_*
 int sphx_sa_tiles_run(sphx_ctx *ctx, int mode, void *forces, const void *pos, const void *vel, const void *newPos,
 	const void *info, const uint32_t *hash, const uint32_t *cellStart, const uint16_t *neibsList, const void *gGam,
