@@ -111,6 +111,7 @@ SIGNATURES = {
     "sphx_postprocess_testpoints_keps": (_i, [_vp] * 9 + [_u32, _u32, _vp]),
     "sphx_wave_gages": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
     "sphx_wave_gages_finish": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),
+    "sphx_save_diagnostics": (_i, [_vp] * 7 + [_u32, _vp]),
     "sphx_euler_basicstep": (_i, [_vp] + [_vp] * 8 + [_u32, _u32, _f, _vp, _f, _i, _f, _f, _f, _i, _vp]),
     "sphx_euler_basicstep_grenier": (_i, [_vp] + [_vp] * 10 + [_u32, _u32, _f, _vp, _f, _i, _f, _f, _f, _i, _vp]),
     "sphx_init_volume": (_i, [_vp] * 5 + [_u32, _vp]),

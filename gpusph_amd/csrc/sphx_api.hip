@@ -1,6 +1,7 @@
 // sphx_api.hip -- context, constants and error plumbing of libsphx (C ABI in include/sphx.h).
 #include "sphx_internal.h"
 #include "gages.h"
+#include "diagnostics.h"
 #include <cstdio>
 #include <cmath>
 #include <cstring>
@@ -114,6 +115,7 @@ extern "C" void sphx_destroy(sphx_ctx *ctx)
 	if (ctx->dem) (void)hipFree(ctx->dem);
 	if (ctx->open_rows) (void)hipFree(ctx->open_rows);
 	sphx_gage_scratch_release(ctx);
+	sphx_diag_scratch_release(ctx);
 	free_granular(ctx);
 	delete ctx->forces_events;
 	delete ctx;

@@ -457,6 +457,17 @@ class HipKernels:
         p = capi.ptr
         capi.check(self.lib.sphx_wave_gages_finish(self.ctx.handle, p(z), p(partials), p(gages), int(num_gages), self._s()))
 
+    # ---- save-time diagnostics (diagnostics.hip): energies and rows per class, the largest |v|^2 and the lowest row without a finite
+    # position over rows [0, n) into out (DIAG_DOUBLES float64; the layout is in include/sphx.h); energy may be None
+    DIAG_MAXSQ = 4 * (D.MAX_FLUID_TYPES + 1)
+    DIAG_NANROW = DIAG_MAXSQ + 1
+    DIAG_DOUBLES = DIAG_MAXSQ + 4
+    DIAG_NO_ROW = 4294967296.0
+
+    def save_diagnostics(self, out, pos, vel, info, hash_, energy, n):
+        p = capi.ptr
+        capi.check(self.lib.sphx_save_diagnostics(self.ctx.handle, p(out), p(pos), p(vel), p(info), p(hash_), p(energy), int(n), self._s()))
+
     # ---- SA open boundaries (ENABLE_INLET_OUTLET): the passes of gpusph_amd/csrc/sa_io.hip behind the driver sequence of
     # gpusph_amd.multigpu (_sa_post_euler_io).  The first five entry points are verified on the GPU; the condition passes, the
     # density summation, the forces, the diffusion and the water depth have run over their own source on the CPU only

@@ -117,6 +117,9 @@ class MultiGpuEngine:
         # torch bumps the counter, the library's own rewrites (sort, filters, halo import) go to the other buffer or clear this
         self._rows_for = None
         self._surface_for = None      # the state (_state_key) whose FG_SURFACE flags are in INFO: wave_gages runs the detection otherwise
+        # m_peakParticleSpeed / m_peakParticleSpeedTime (src/GPUSPH.cc:88-89): the largest speed any save_diagnostics saw, and when
+        self.peak_particle_speed = np.float32(0.0)
+        self.peak_particle_speed_time = 0.0
         self._rows_follow = (not self.sa and not self.grenier and not self.effvisc_on and hasattr(kernels, "eos_rows_follow_euler")
                              and problem.simparams.sph_formulation in (D.SPH_F1, D.SPH_F2))
         if self._rows_follow:
@@ -907,6 +910,61 @@ class MultiGpuEngine:
                 f.write(commonwriter.wave_gage_header(len(z)))
             f.write(commonwriter.wave_gage_line(self.time(), z))
         return z
+
+    # ------------------------------------------------------------------ save-time diagnostics
+    def save_diagnostics(self):
+        """What GPUSPH::doWrite takes from its host copy of the state besides the gages (src/GPUSPH.cc:1597-1647,1672-1684),
+        computed on the device (diagnostics.hip): dict(energy = float64 [MAX_FLUID_TYPES + 1, 3], kinetic, potential and internal
+        energy per fluid with the non-fluid class last; rows = the number of active rows per class; max_speed = the largest
+        length(vel), float32; nan_row = (rank, row) of the first active particle without a finite position, or None).  Every rank
+        counts the rows it owns, never its halo; the ranks add their sums in double in rank order, take the largest speed and
+        the nan_row of the lowest rank.  Inactive rows count for nothing, and kinetic and potential energy are formed without
+        ENABLE_INTERNAL_ENERGY too (internal = 0).  Keeps peak_particle_speed and its time up to date (a strict >, :1681-1684) and
+        warns, naming the row, when nan_row is set.  Synchronises."""
+        K, dev = self.k, self.device
+        out = torch.empty(K.DIAG_DOUBLES, dtype=torch.float64, device=dev)
+        K.save_diagnostics(out, self.pos, self.vel, self.info, self.hash, self.energy if self.energy_on else None, self.n_int)
+        mine = out.cpu().numpy()
+        sums, pairs = mine[:K.DIAG_MAXSQ], [(mine[K.DIAG_MAXSQ], mine[K.DIAG_NANROW])]
+        if self.world > 1:
+            d_sums = out[:K.DIAG_MAXSQ].contiguous()
+            self.transport.allreduce_sum(d_sums)
+            sums = d_sums.cpu().numpy()
+            got = self.transport.allgather_pair(int(mine[K.DIAG_MAXSQ:K.DIAG_MAXSQ + 1].view(np.uint64)[0]),
+                                                int(mine[K.DIAG_NANROW:K.DIAG_NANROW + 1].view(np.uint64)[0]), dev)
+            pairs = [tuple(np.array(v, dtype=np.uint64).view(np.float64)) for v in got]
+        sums = sums.reshape(D.MAX_FLUID_TYPES + 1, 4)
+        max_speed = np.sqrt(np.float32(max(v[0] for v in pairs)))         # ONE correctly rounded float sqrt of the largest |v|^2
+        nan_row = next(((r, int(v[1])) for r, v in enumerate(pairs) if v[1] < K.DIAG_NO_ROW), None)
+        if max_speed > self.peak_particle_speed:
+            self.peak_particle_speed = max_speed
+            self.peak_particle_speed_time = self.time()
+        if nan_row is not None:
+            import warnings
+            warnings.warn("particle %d of rank %d has a NaN position at iteration %d, time %g"
+                          % (nan_row[1], nan_row[0], self.iterations, self.time()), RuntimeWarning, stacklevel=2)
+        return {"energy": sums[:, :3].copy(), "rows": sums[:, 3].astype(np.int64), "max_speed": max_speed, "nan_row": nan_row}
+
+    def peak_speed_line(self):
+        """the line GPUSPH prints at the end of a run (src/GPUSPH.cc:775-776) from the peak over the save_diagnostics calls so far"""
+        v = float(self.peak_particle_speed)
+        return ("Peak particle speed was ~%g m/s at %g s -> can set maximum vel %.2g for this problem\n"
+                % (v, self.peak_particle_speed_time, v*1.1))
+
+    def write_energy(self, path):
+        """one line of energy.txt (CommonWriter::write_energy, src/writers/CommonWriter.cc:226-241) for the current state; the header
+        (:53-70) goes first into a new file.  Every rank takes part in the reading, rank 0 writes.  Returns save_diagnostics()."""
+        from . import commonwriter
+        d = self.save_diagnostics()
+        if self.rank != 0:
+            return d
+        nf = self.problem.physparams.numFluids()
+        new = not os.path.exists(path) or os.path.getsize(path) == 0
+        with open(path, "a") as f:
+            if new:
+                f.write(commonwriter.energy_header(nf))
+            f.write(commonwriter.energy_line(self.time(), d["energy"], nf))
+        return d
 
     def download_internal(self):
         n = self.n_int

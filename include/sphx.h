@@ -598,6 +598,39 @@ int sphx_wave_gages(sphx_ctx *ctx, double *d_partials, const double *gages, uint
 	const void *pos, const void *info, const uint32_t *hash, uint32_t numParticles, void *stream);
 int sphx_wave_gages_finish(sphx_ctx *ctx, double *d_z, const double *d_partials, const double *gages, uint32_t numGages, void *stream);
 
+/* ---- save-time diagnostics (GPUSPH::doWrite, src/GPUSPH.cc:1597-1647,1672-1684) ---------------- */
+/* The energy budget per fluid that CommonWriter keeps in energy.txt, the largest particle speed and the first particle without a
+ * finite position, over rows [0, numParticles), without the host copy of the state the reference takes them from.  Every ACTIVE row
+ * (finite pos.w) adds, in double precision on the global position gp = (cell size)*(cell + 1/2) + local position + world origin
+ * (calcGlobalPosOffset; cell size, world origin and gravity as uploaded: floats, widened), with m = pos.w
+ *     kinetic    m (double)((vx vx + vy vy + vz vz)/2)         the bracket in float, left to right
+ *     potential  -m (gp.x gx + gp.y gy + gp.z gz)              in double, left to right
+ *     internal   m (double)intEnergy[row]                      0 when intEnergy is NULL
+ * to its class, the fluid number of a fluid particle and SPHX_MAX_FLUIDS for everybody else.  No FMA contraction: the terms are
+ * those of a host loop, only the order of the sums differs.  d_out: SPHX_DIAG_DOUBLES doubles on the device,
+ *     d_out[4 c + 0..3]   kinetic, potential, internal energy and the number of rows of class c = 0 .. SPHX_MAX_FLUIDS
+ *     d_out[SPHX_DIAG_MAXSQ]    the largest vx vx + vy vy + vz vz of an active row (a float, widened; 0 without rows; NaN is
+ *                               ignored as fmax does).  Its float square root, taken once, is the largest length(vel): sqrt is monotone
+ *     d_out[SPHX_DIAG_NANROW]   the lowest active row whose global position is not finite, SPHX_DIAG_NO_ROW (2^32, behind every
+ *                               uint32 row) when there is none
+ *     then zeros up to SPHX_DIAG_DOUBLES
+ * Deterministic: no floating-point atomics, the grid depends on numParticles alone, the same state gives the same bits.  Several
+ * ranks combine theirs: the first SPHX_DIAG_MAXSQ doubles are sums (sphx_halo_allreduce_sum_f64), the largest speed and the lowest
+ * rank with a row travel as a pair of bit patterns (sphx_halo_allgather_u64x2).  numParticles = 0: zeros and SPHX_DIAG_NO_ROW.
+ * No constants, a NULL d_out, or NULL pos / vel / info / hash with numParticles > 0: SPHX_ERR_INVALID.
+ * Where this leaves the reference:
+ *   - an inactive row (NaN mass) counts for nothing; the reference's sums would be NaN
+ *   - kinetic and potential energy are formed whether or not the run has ENABLE_INTERNAL_ENERGY (intEnergy NULL: internal = 0); the
+ *     reference writes zeros in all three columns then
+ *   - a non-finite position of an active row poisons the potential energy of its class as in the reference; d_out[SPHX_DIAG_NANROW]
+ *     says which row it is (the reference prints a warning for the first one) */
+#define SPHX_DIAG_MAXSQ   (4*(SPHX_MAX_FLUIDS + 1))
+#define SPHX_DIAG_NANROW  (SPHX_DIAG_MAXSQ + 1)
+#define SPHX_DIAG_DOUBLES (SPHX_DIAG_MAXSQ + 4)
+#define SPHX_DIAG_NO_ROW  4294967296.0
+int sphx_save_diagnostics(sphx_ctx *ctx, double *d_out, const void *pos, const void *vel, const void *info,
+	const uint32_t *hash, const float *intEnergy, uint32_t numParticles, void *stream);
+
 /* ---- AbstractIntegrationEngine ------------------------------------------------------------ */
 /* basicstep (src/cuda/euler.cu:329-366).  dt is the step's dt or dt/2 exactly as the
  * reference passes it; if d_dt is not NULL the kernel instead uses d_dt[0]*dt_scale read on
