@@ -121,6 +121,14 @@ extern "C" void sphx_destroy(sphx_ctx *ctx)
 	delete ctx;
 }
 
+// tests only, not part of include/sphx.h: what the HOST knows of the last tiling's overflow flag (sphx_ctx::tiles_overflow: -1 not
+// seen yet, 0 usable, 1 overflowed), as the last pass left it.  Looks for nothing and waits for nothing: a test reads here which of
+// the protocol's branches a pass it has just enqueued took (tiled launch + guarded stand-by, or no tiled launch at all)
+extern "C" int sphx_dbg_tiles_host_state(sphx_ctx *ctx)
+{
+	return ctx ? ctx->tiles_overflow : -2;
+}
+
 // number of sort bins: one per (cell type, cell) + 1 for inactive particles (CELL_HASH_MAX)
 static uint32_t num_bins(const sphx_ctx *ctx)
 {
