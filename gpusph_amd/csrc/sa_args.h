@@ -107,6 +107,7 @@ struct SaDensitySumArgs {
 	float dt;
 	uint32_t *openList;           // ... sa_density_sum_wall_kernel<true> appends the particles with an open segment in reach ([0] = count)
 	const float4 *boundElementNew; // ENABLE_MOVING_BODIES (sa_density_sum_kernel<.., true>): BUFFER_BOUNDELEMENTS of the new state
+	float deltap;                 // SPH_HA (sa_density_sum_kernel<.., .., true>): deltap^3 is the reference volume of the volume fractions
 };
 
 // Brezzi density diffusion with SA_BOUNDARY: see sa_density_diffusion_kernel (sa_bounds.hip)

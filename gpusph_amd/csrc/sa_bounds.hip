@@ -254,7 +254,14 @@ sa_init_gamma_kernel(DevParams p, SaGammaArgs a)
 // OPEN: a run with open boundaries (laminar): the viscous term of a fluid <- vertex pair and of a boundary element sees the
 // relative velocity plus the relative Eulerian velocity (get_viscous_relVel, forces_kernel.def:2494-2507; no normal part is taken
 // out for the segment of an open face, :2703-2708), and the gamma CFL term gains compute_gamma_cfl_open_boundary (:1485-1497)
-template<bool KEPS, bool OPEN = false>
+// HA: formulation<SPH_HA> (Hu & Adams, BiFluidPoiseuilleSA's set: several fluids, density summation, laminar).  The pressure is
+// precalculated as P itself (precalc_pressure :457-468) and weighted by squared volumes: a particle neighbour contributes
+// (P_a V_a^2 theta_b/theta_a + P_b V_b^2 theta_a/theta_b)/m_a F r_ab with the ACTUAL volumes V = m/rho, theta = 1 for a fluid
+// particle and V/deltap^3 for a vertex (:2330-2355, :2431-2447, calc_volume_fraction :1524-1557); a boundary element
+// (P_a V_a^2 + P_s V_s^2)/V_s/m_a |grad gamma_as| n_s with the reference volumes V_a = m_a/rho_a/theta_a (theta_a = 1: a fluid
+// particle) and V_s = deltap^3 rho0_s/rho_s (:2289-2328, :2395-2412).  The viscous terms, the gamma CFL term and the fix-ups are
+// those of every formulation; the continuity equation is not built for it (sa_forces_check).  List walker only: nothing of it is tiled.
+template<bool KEPS, bool OPEN = false, bool HA = false>
 __global__ void __launch_bounds__(SPHX_BLOCK_FORCES)
 sa_forces_kernel(DevParams p, SaForcesArgs a)
 {
@@ -276,7 +283,10 @@ sa_forces_kernel(DevParams p, SaForcesArgs a)
 				// keps_particle_data :633-655, eulerVel_particle_data :553-561; pressure_for_precalc :389-401: P + 2/3 k/rho
 				const float p_k = KEPS ? a.tke[index] : 0.0f, p_e = KEPS ? a.eps[index] : 0.0f, p_turb = KEPS ? a.turbvisc[index] : 0.0f;
 				const float4 p_euler = (KEPS || OPEN) ? a.eulerVel[index] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-				const float p_precalc = KEPS ? (sa_P(p, vel.w, fl) + 2.0f*p_k/p_rho/3.0f)/(p_rho*p_rho) : sa_P(p, vel.w, fl)/(p_rho*p_rho);
+				const float p_precalc = HA ? sa_P(p, vel.w, fl) :
+					KEPS ? (sa_P(p, vel.w, fl) + 2.0f*p_k/p_rho/3.0f)/(p_rho*p_rho) : sa_P(p, vel.w, fl)/(p_rho*p_rho);
+				const float p_volume = HA ? pos.w/p_rho : 0.0f;              // HA: actual volume; theta of a fluid particle is 1
+				const float ref_volume0 = HA ? a.deltap*a.deltap*a.deltap : 0.0f;
 				float diff_k = 0.0f, diff_e = 0.0f, ce2yap = 1.92f, txx = 0.0f, txy = 0.0f, txz = 0.0f, tyy = 0.0f, tyz = 0.0f, tzz = 0.0f;
 				const bool density_sum = (p.simflags & SPHX_ENABLE_DENSITY_SUM) != 0;
 				const bool newtonian = p.rheology == SPHX_NEWTONIAN;
@@ -297,7 +307,8 @@ sa_forces_kernel(DevParams p, SaForcesArgs a)
 					const float f = qm2*qm2*qm2*p.fcoeff;
 					const uint32_t nfl = FLUID_NUM(a.info[j]);
 					const float n_rho = (nvel.w + 1.0f)*p.rho0[nfl];
-					const float n_precalc = KEPS ? (sa_P(p, nvel.w, nfl) + 2.0f*a.tke[j]/n_rho/3.0f)/(n_rho*n_rho) : sa_P(p, nvel.w, nfl)/(n_rho*n_rho);
+					const float n_precalc = HA ? sa_P(p, nvel.w, nfl) :
+						KEPS ? (sa_P(p, nvel.w, nfl) + 2.0f*a.tke[j]/n_rho/3.0f)/(n_rho*n_rho) : sa_P(p, nvel.w, nfl)/(n_rho*n_rho);
 					const float nmass = npos.w;
 					if (!density_sum) {
 						float DrDt = nmass*vel_dot_pos*f;
@@ -312,7 +323,14 @@ sa_forces_kernel(DevParams p, SaForcesArgs a)
 						}
 						force.w += DrDt;
 					}
-					const float s = (p_precalc + n_precalc)*nmass*f;
+					float s;
+					if (HA) {
+						const float n_volume = nmass/n_rho;
+						const float p_theta = 1.0f, n_theta = vertexSection ? n_volume/ref_volume0 : 1.0f;
+						const float term = p_precalc*p_volume*p_volume*n_theta/p_theta + n_precalc*n_volume*n_volume*p_theta/n_theta;
+						s = term/pos.w*f;
+					} else
+						s = (p_precalc + n_precalc)*nmass*f;
 					float dx = 0.0f, dy = 0.0f, dz = 0.0f;
 					dx -= s*rx; dy -= s*ry; dz -= s*rz;
 					if (KEPS && newtonian) {
@@ -354,7 +372,7 @@ sa_forces_kernel(DevParams p, SaForcesArgs a)
 					const float vx = vel.x - nvel.x, vy = vel.y - nvel.y, vz = vel.z - nvel.z;
 					const uint32_t nfl = FLUID_NUM(a.info[j]);
 					const float n_rho = (nvel.w + 1.0f)*p.rho0[nfl];
-					const float n_precalc = sa_P(p, nvel.w, nfl)/(n_rho*n_rho);
+					const float n_precalc = HA ? sa_P(p, nvel.w, nfl) : sa_P(p, nvel.w, nfl)/(n_rho*n_rho);
 					const float4 be = a.boundElement[j];
 					const V3 ns = v3(be.x, be.y, be.z);
 					const float inv_h = 1.0f/p.slength;
@@ -386,7 +404,14 @@ sa_forces_kernel(DevParams p, SaForcesArgs a)
 						force.w += DrDt;
 					}
 					const float n_precalc_k = KEPS ? (sa_P(p, nvel.w, nfl) + 2.0f*a.tke[j]/n_rho/3.0f)/(n_rho*n_rho) : n_precalc;
-					const float ps = (p_precalc + n_precalc_k)*n_rho*ggamAS;
+					float ps;
+					if (HA) {
+						const float p_theta = 1.0f;
+						const float p_ref_volume = pos.w/p_rho/p_theta;
+						const float n_ref_volume = ref_volume0*p.rho0[nfl]/n_rho;
+						ps = (p_precalc*p_ref_volume*p_ref_volume + n_precalc*n_ref_volume*n_ref_volume)/n_ref_volume/pos.w*ggamAS;
+					} else
+						ps = (p_precalc + n_precalc_k)*n_rho*ggamAS;
 					float dx = 0.0f, dy = 0.0f, dz = 0.0f;
 					dx += ps*be.x; dy += ps*be.y; dz += ps*be.z;
 					if (KEPS) {
@@ -614,7 +639,10 @@ sa_integrate_gamma_kernel(DevParams p, SaIntGammaArgs a)
 // boundElement, that of the new state from boundElementNew (the Euler step turned it, sphx_sa_update_normals), the corners are
 // set up once per normal; gamma of the VERTEX rows is integrated by the same boundary terms instead of copied
 // (integrateGammaDevice<PT_VERTEX>, density_sum_impl src/cuda/euler.cu:112-160); boundary rows are left to the segment condition
-template<bool OPEN, bool MOVING = false>
+// HA: formulation<SPH_HA>, rho_a = m_a/theta_a sum_b theta_b W_ab in the place of sum_b m_b W_ab: the neighbour's mass in the volumic
+// sums becomes m_a/theta_a theta_b, theta = (m/rho0)/deltap^3 from the INITIAL volumes of fluid and vertex particles alike
+// (computeDensitySumVolumicTerms<SPH_HA>, density_sum_kernel.cu:253-322).  Solid walls at rest, list walker only.
+template<bool OPEN, bool MOVING = false, bool HA = false>
 __global__ void __launch_bounds__(128)
 sa_density_sum_kernel(DevParams p, SaDensitySumArgs a)
 {
@@ -644,12 +672,20 @@ sa_density_sum_kernel(DevParams p, SaDensitySumArgs a)
 		const float rx = pcx - nN.x, ry = pcy - nN.y, rz = pcz - nN.z;
 		const float qx = (pcx - nNp1.x) + dx, qy = (pcy - nNp1.y) + dy, qz = (pcz - nNp1.z) + dz;
 		const bool openNeib = OPEN && SA_IS_OPEN(a.info[j]);
+		float nmass = nN.w;
+		if (HA) {
+			const float p_volume0 = posN.w/p.rho0[FLUID_NUM(info)];
+			const float n_volume0 = nN.w/p.rho0[FLUID_NUM(a.info[j])];
+			const float p_theta = p_volume0/(a.deltap*a.deltap*a.deltap);
+			const float n_theta = n_volume0/(a.deltap*a.deltap*a.deltap);
+			nmass = posN.w/p_theta*n_theta;
+		}
 		if (!openNeib) {
 			const float rN = sqrtf(rx*rx + ry*ry + rz*rz);
-			sumPmwN -= nN.w*kernel_W<SPHX_WENDLAND>(p, rN);
+			sumPmwN -= nmass*kernel_W<SPHX_WENDLAND>(p, rN);
 		}
 		const float rNp1 = sqrtf(qx*qx + qy*qy + qz*qz);
-		if (rNp1 < p.influenceradius) sumPmwNp1 += nN.w*kernel_W<SPHX_WENDLAND>(p, rNp1);
+		if (rNp1 < p.influenceradius) sumPmwNp1 += nmass*kernel_W<SPHX_WENDLAND>(p, rNp1);
 		if (openNeib) {
 			const float4 e = a.oldEulerVel[j], v = a.oldVel[j];
 			const float ex = rx + a.dt*(e.x - v.x), ey = ry + a.dt*(e.y - v.y), ez = rz + a.dt*(e.z - v.z);
@@ -735,7 +771,11 @@ sa_density_sum_kernel(DevParams p, SaDensitySumArgs a)
 // OPEN: with ENABLE_INLET_OUTLET the segments of PRESSURE-driven open faces exchange density with the fluid as a fluid neighbour
 // would, with |grad gamma_as| / r_as in the place of V_b F, no diffusion coefficient, evaluated in double as the literals of the
 // reference's expression make it (:1836-1852, 4536-4582)
-template<bool OPEN>
+// HA: formulation<SPH_HA> (:1786-1824).  2/(rho_a + rho_b) becomes 2/(m_a (1/V_a + theta_b/(theta_a V_b))) with the actual volumes
+// V = m/rho and theta from the INITIAL volumes (1 for a fluid particle, (m/rho0)/deltap^3 for a vertex); the reference's 1./p_volume
+// is a double literal, so the whole term is formed in double and rounded once when it is added; VERTEX neighbours take part as well
+// as fluid ones.  Solid walls, list walker only.
+template<bool OPEN, bool HA = false>
 __global__ void __launch_bounds__(128)
 sa_density_diffusion_kernel(DevParams p, SaDiffusionArgs a)
 {
@@ -752,7 +792,7 @@ sa_density_diffusion_kernel(DevParams p, SaDiffusionArgs a)
 	const float pres = sa_P(p, vel.w, fl);
 	const int3 gridPos = grid_pos_from_hash(p, a.hash[index] & CELLTYPE_BITMASK);
 	float DrDt = 0.0f;
-	for_each_neib<PT_FLUID>(p, a, index, pos, gridPos, [&](uint32_t j, const float4 &npos, float rx, float ry, float rz) {
+	auto volumic = [&](bool vertexSection, uint32_t j, const float4 &npos, float rx, float ry, float rz) {
 		const float r = sqrtf(rx*rx + ry*ry + rz*rz);
 		if (!is_active_w(npos.w)) return;
 		if (r >= p.influenceradius) return;
@@ -763,9 +803,19 @@ sa_density_diffusion_kernel(DevParams p, SaDiffusionArgs a)
 		const float f = qm2*qm2*qm2*p.fcoeff;
 		const float gdotr = p.gravity[0]*rx + p.gravity[1]*ry + p.gravity[2]*rz;
 		float n = 0.0f;
-		n += p.densityDiffCoeff*((2.0f/(rho + neib_rho))*(pres - sa_P(p, nvel.w, nfl)) - gdotr)*npos.w/neib_rho*f*a.dt*2.0f*rho;
+		if (HA) {
+			const float n_volume0 = npos.w/p.rho0[nfl];
+			const float p_theta = 1.0f, n_theta = vertexSection ? n_volume0/(a.deltap*a.deltap*a.deltap) : 1.0f;
+			const float p_volume = pos.w/rho, n_volume = npos.w/neib_rho;
+			n = (float)(n + p.densityDiffCoeff*(2.0f/(pos.w*(1./p_volume + n_theta/(p_theta*n_volume)))*(pres - sa_P(p, nvel.w, nfl)) - gdotr)
+				*npos.w/neib_rho*f*a.dt*2.0f*rho);
+		} else
+			n += p.densityDiffCoeff*((2.0f/(rho + neib_rho))*(pres - sa_P(p, nvel.w, nfl)) - gdotr)*npos.w/neib_rho*f*a.dt*2.0f*rho;
 		DrDt += n;
-	});
+	};
+	for_each_neib<PT_FLUID>(p, a, index, pos, gridPos, [&](uint32_t j, const float4 &np_, float rx, float ry, float rz) { volumic(false, j, np_, rx, ry, rz); });
+	if (HA)
+		for_each_neib<PT_VERTEX>(p, a, index, pos, gridPos, [&](uint32_t j, const float4 &np_, float rx, float ry, float rz) { volumic(true, j, np_, rx, ry, rz); });
 	if (OPEN)
 	for_each_neib<PT_BOUNDARY>(p, a, index, pos, gridPos, [&](uint32_t j, const float4 &npos, float rx, float ry, float rz) {
 		const float r = sqrtf(rx*rx + ry*ry + rz*rz);
@@ -1071,8 +1121,12 @@ static int sa_forces_check(sphx_ctx *ctx, const char *who)
 	// BUFFER_RB_FORCES with SA_BOUNDARY): the pressure force on their elements is sphx_sa_body_pressure_forces, below.
 	if (q.simflags & (SPHX_ENABLE_XSPH | SPHX_ENABLE_PLANES))
 		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx_sa: SA forces are built without XSPH and planes");
-	if (q.sph_formulation != SPHX_SPH_F1)
-		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx_sa: SA forces are built for SPH_F1");
+	if (q.sph_formulation != SPHX_SPH_F1 && q.sph_formulation != SPHX_SPH_HA)
+		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx_sa: SA forces are built for SPH_F1 and SPH_HA");
+	// SPH_HA (BiFluidPoiseuilleSA's set): sphx_set_constants has refused everything but density summation with dynamic gamma,
+	// laminar flow, no or Brezzi diffusion, solid walls at rest
+	if (q.sph_formulation == SPHX_SPH_HA && !dsum)
+		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx_sa: SPH_HA with SA_BOUNDARY is built for ENABLE_DENSITY_SUM (not for the continuity equation)");
 	// density diffusion: Brezzi with the density summation (a pass of its own), Ferrari with the continuity equation (a term of the
 	// forces pass: Spheric2SA's set); Colagrossi has no SA form in the reference either
 	if (q.densitydiffusiontype == SPHX_FERRARI) {
@@ -1169,6 +1223,9 @@ static int sa_forces_impl(sphx_ctx *ctx, void *forces, float *cfl, float *cflGam
 		a.dkde = ke->dkde; a.cflKeps = ke->cflKeps; a.epsilon = ke->epsilon;
 		if (ke->cflKeps && numBlocks > blocks) SPHX_HIP(hipMemsetAsync(ke->cflKeps + cflOffset + blocks, 0, sizeof(float)*(numBlocks - blocks), st));
 		sa_forces_kernel<true><<<blocks, SPHX_BLOCK_FORCES, 0, st>>>(ctx->dev, a);
+	} else if (ctx->params.sph_formulation == SPHX_SPH_HA) {
+		// the list walker is the whole pass: neither the tiled window nor the one-element-per-lane wall kernel knows SPH_HA
+		sa_forces_kernel<false, false, true><<<blocks, SPHX_BLOCK_FORCES, 0, st>>>(ctx->dev, a);
 	} else {
 		rc = sa_forces_tiles_and_walls(ctx, a, false, numParticles, st);
 		if (rc != SPHX_OK) return rc;
@@ -1476,21 +1533,35 @@ extern "C" int sphx_sa_density_sum(sphx_ctx *ctx, void *newVel, void *newGGam, v
 	uint32_t numParticles, uint32_t particleRangeEnd, float dt, int step, float t, float epsilon,
 	float deltap, float slength, float influenceradius, void *stream)
 {
-	(void)dt; (void)step; (void)t; (void)epsilon; (void)deltap;
+	(void)dt; (void)step; (void)t; (void)epsilon;
 	int rc = sa_check(ctx, "density_sum called without SA_BOUNDARY");
 	if (rc != SPHX_OK) return rc;
 	if (!(ctx->params.simflags & SPHX_ENABLE_DENSITY_SUM) || (ctx->params.simflags & SPHX_ENABLE_GAMMA_QUADRATURE))
 		return sphx_set_error(SPHX_ERR_INVALID, "sphx_sa_density_sum: needs ENABLE_DENSITY_SUM with dynamic gamma");
 	if (ctx->params.simflags & SPHX_ENABLE_MOVING_BODIES)
 		return sphx_set_error(SPHX_ERR_INVALID, "sphx_sa_density_sum: with ENABLE_MOVING_BODIES the boundary elements are double buffered: call sphx_sa_density_sum_moving");
-	if (ctx->params.sph_formulation != SPHX_SPH_F1 && ctx->params.sph_formulation != SPHX_SPH_F2)
-		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx_sa_density_sum: SPH_HA is not built");
+	const bool ha = ctx->params.sph_formulation == SPHX_SPH_HA;
+	if (ctx->params.sph_formulation != SPHX_SPH_F1 && ctx->params.sph_formulation != SPHX_SPH_F2 && !ha)
+		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx_sa_density_sum: built for SPH_F1, SPH_F2 and SPH_HA");
 	SPHX_REQUIRE(newVel && newGGam && forces && oldPos && newPos && oldVel && oldGGam && boundElements && vertPos0 && vertPos1 && vertPos2 &&
 		info && hash && cellStart && neibsList, "sphx_sa_density_sum: missing buffer");
 	SPHX_REQUIRE(newGGam != oldGGam, "sphx_sa_density_sum: gamma is double buffered");
 	SPHX_REQUIRE(slength == ctx->params.slength && influenceradius == ctx->params.influenceradius,
 		"sphx_sa_density_sum: slength / influenceradius differ from the uploaded constants");
+	SPHX_REQUIRE(!ha || deltap > 0.0f, "sphx_sa_density_sum: SPH_HA needs deltap (the reference volume of its volume fractions)");
 	SaDensitySumArgs a;
+	if (ha) {      // the list walker is the whole pass: the tiled window and the wall kernel sum the neighbours' masses
+		if (!particleRangeEnd) return SPHX_OK;
+		a = {};
+		a.newVel = (float4*)newVel; a.newGGam = (float4*)newGGam; a.forces = (float4*)forces;
+		a.oldPos = (const float4*)oldPos; a.pos = (const float4*)newPos; a.oldVel = (const float4*)oldVel; a.oldGGam = (const float4*)oldGGam;
+		sa_set_elements(a, boundElements, vertPos0, vertPos1, vertPos2);
+		sa_set_lists(a, info, hash, cellStart, neibsList);
+		a.numParticles = particleRangeEnd; a.deltap = deltap;
+		sa_density_sum_kernel<false, false, true><<<div_up_u(particleRangeEnd, 128), 128, 0, (hipStream_t)stream>>>(ctx->dev, a);
+		SPHX_LAUNCH_CHECK("sa_density_sum_kernel<SPH_HA>");
+		return SPHX_OK;
+	}
 	rc = sa_density_sum_begin(ctx, a, false, false, newVel, newGGam, forces, oldPos, newPos, oldVel, nullptr, oldGGam, boundElements, nullptr,
 		vertPos0, vertPos1, vertPos2, info, hash, cellStart, neibsList, numParticles, particleRangeEnd, 0.0f, (hipStream_t)stream);
 	if (rc != SPHX_OK || !particleRangeEnd) return rc;
@@ -1565,16 +1636,25 @@ extern "C" int sphx_sa_compute_density_diffusion(sphx_ctx *ctx, void *forces, co
 	const void *info, const uint32_t *hash, const uint32_t *cellStart, const uint16_t *neibsList,
 	uint32_t numParticles, uint32_t particleRangeEnd, float deltap, float slength, float influenceradius, float dt, void *stream)
 {
-	(void)deltap;
 	int rc = sa_check(ctx, "compute_density_diffusion called without SA_BOUNDARY");
 	if (rc != SPHX_OK) return rc;
-	if (ctx->params.densitydiffusiontype != SPHX_BREZZI || !(ctx->params.simflags & SPHX_ENABLE_DENSITY_SUM) ||
-		ctx->params.sph_formulation == SPHX_SPH_HA)
+	if (ctx->params.densitydiffusiontype != SPHX_BREZZI || !(ctx->params.simflags & SPHX_ENABLE_DENSITY_SUM))
 		return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx_sa_compute_density_diffusion: built for Brezzi diffusion with density summation");
 	SPHX_REQUIRE(forces && pos && vel && gGam && info && hash && cellStart && neibsList, "sphx_sa_compute_density_diffusion: missing buffer");
 	SPHX_REQUIRE(slength == ctx->params.slength && influenceradius == ctx->params.influenceradius,
 		"sphx_sa_compute_density_diffusion: slength / influenceradius differ from the uploaded constants");
 	SaDiffusionArgs a;
+	if (ctx->params.sph_formulation == SPHX_SPH_HA) {      // the list walker is the whole pass (fluid and vertex neighbours)
+		SPHX_REQUIRE(deltap > 0.0f, "sphx_sa_compute_density_diffusion: SPH_HA needs deltap (the reference volume of its volume fractions)");
+		if (!particleRangeEnd) return SPHX_OK;
+		a = {};
+		a.forces = (float4*)forces; a.pos = (const float4*)pos; a.vel = (const float4*)vel; a.gGam = (const float4*)gGam;
+		sa_set_lists(a, info, hash, cellStart, neibsList);
+		a.numParticles = particleRangeEnd; a.dt = dt; a.deltap = deltap;
+		sa_density_diffusion_kernel<false, true><<<div_up_u(particleRangeEnd, 128), 128, 0, (hipStream_t)stream>>>(ctx->dev, a);
+		SPHX_LAUNCH_CHECK("sa_density_diffusion_kernel<SPH_HA>");
+		return SPHX_OK;
+	}
 	bool walker;
 	rc = sa_density_diffusion_begin(ctx, a, &walker, false, forces, pos, vel, gGam, nullptr, nullptr, nullptr, nullptr, info, hash, cellStart, neibsList,
 		numParticles, particleRangeEnd, 0.0f, dt, (hipStream_t)stream);

@@ -261,9 +261,39 @@ extern "C" int sphx_set_constants(sphx_ctx *ctx, const sphx_params *sp)
 	if (sp->sph_formulation < SPHX_SPH_F1 || sp->sph_formulation > SPHX_SPH_HA)
 		return sphx_set_error(SPHX_ERR_INVALID, "sphx: invalid SPH formulation");
 	if (sp->sph_formulation == SPHX_SPH_HA) {
-		// Hu & Adams (BiFluidPoiseuille): rheology.hip's forces kernel
+		// Hu & Adams (BiFluidPoiseuille): rheology.hip's forces kernel with DYN_BOUNDARY, the SPH_HA variants of sa_bounds.hip's list
+		// walkers with SA_BOUNDARY
+		if (sp->boundarytype == SPHX_SA_BOUNDARY) {
+			// BiFluidPoiseuilleSA's set (src/problems/BiFluidPoiseuille.inc:45-59): density summation with dynamic gamma, laminar,
+			// INVISCID or NEWTONIAN with MORRIS, no or Brezzi diffusion, solid walls at rest, any number of fluids.  LithostaticSA's
+			// set (GRANULAR) is not: its Jacobi vectors need boundary-element terms that are not built
+			if (sp->rheologytype == SPHX_GRANULAR)
+				return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: SPH_HA with SA_BOUNDARY: the GRANULAR rheology (LithostaticSA) is not built");
+			if (sp->turbmodel == SPHX_KEPSILON)
+				return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: SPH_HA with SA_BOUNDARY: the k-epsilon model is not built");
+			if (sp->turbmodel != SPHX_LAMINAR_FLOW)
+				return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: SPH_HA with SA_BOUNDARY is built for LAMINAR_FLOW");
+			if (sp->simflags & SPHX_ENABLE_GAMMA_QUADRATURE)
+				return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: SPH_HA with SA_BOUNDARY: ENABLE_GAMMA_QUADRATURE is not built (dynamic gamma is)");
+			if (!(sp->simflags & SPHX_ENABLE_DENSITY_SUM))
+				return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: SPH_HA with SA_BOUNDARY: the continuity equation is not built (ENABLE_DENSITY_SUM is)");
+			if (sp->densitydiffusiontype == SPHX_FERRARI)
+				return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: SPH_HA with SA_BOUNDARY: Ferrari density diffusion is not built (Brezzi is)");
+			if (sp->densitydiffusiontype != SPHX_DENSITY_DIFFUSION_NONE && sp->densitydiffusiontype != SPHX_BREZZI)
+				return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: SPH_HA with SA_BOUNDARY is built without density diffusion or with Brezzi");
+			if (sp->simflags & SPHX_ENABLE_INLET_OUTLET)
+				return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: SPH_HA with SA_BOUNDARY: open boundaries are not built (untested in the reference, src/cuda/density_sum_kernel.cu:160)");
+			if (sp->simflags & SPHX_ENABLE_MOVING_BODIES)
+				return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: SPH_HA with SA_BOUNDARY: moving bodies are not built");
+			if (sp->simflags & SPHX_ENABLE_REPACKING)
+				return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: SPH_HA with SA_BOUNDARY: repacking is not built");
+			if (sp->simflags & (SPHX_ENABLE_XSPH | SPHX_ENABLE_PLANES))
+				return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: SPH_HA with SA_BOUNDARY is built without XSPH and planes");
+			if (sp->rheologytype > SPHX_NEWTONIAN || (sp->rheologytype == SPHX_NEWTONIAN && sp->viscmodel != SPHX_MORRIS))
+				return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: SPH_HA with SA_BOUNDARY is built for INVISCID, or NEWTONIAN with the MORRIS viscous model");
+		} else
 		if (sp->boundarytype != SPHX_DYN_BOUNDARY || sp->turbmodel != SPHX_LAMINAR_FLOW)
-			return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: SPH_HA is built for DYN_BOUNDARY and LAMINAR_FLOW");
+			return sphx_set_error(SPHX_ERR_UNSUPPORTED, "sphx: SPH_HA is built for DYN_BOUNDARY and LAMINAR_FLOW (SA_BOUNDARY: the density summation form)");
 	}
 	if (sp->sph_formulation == SPHX_SPH_GRENIER) {
 		// the option set of the reference's Grenier problems (Bubble, LockExchange, RTInstability, OilJet): Wendland kernel,

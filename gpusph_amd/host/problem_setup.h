@@ -232,6 +232,23 @@ static SimFramework *make_framework(Case const& c)
 			RHODIFF == BREZZI, densitydiffusion<BREZZI>(),
 			RHODIFF == COLAGROSSI, densitydiffusion<COLAGROSSI>()
 		);
+	} else if (name == "BiFluidPoiseuilleSA") {   // the same expression with the SA defines of BiFluidPoiseuilleSA.cu:27-28 (the SATwoFluidBox mirror)
+		const DensityDiffusionType RHODIFF = (DensityDiffusionType)(int)num(c, "rhodiff");
+		SETUP_FRAMEWORK(
+			formulation<SPH_HA>,
+			rheology<NEWTONIAN>,
+			turbulence_model<LAMINAR_FLOW>,
+			computational_visc<DYNAMIC>,
+			visc_model<MORRIS>,
+			visc_average<HARMONIC>,
+			boundary<SA_BOUNDARY>,
+			periodicity<PERIODIC_XY>,
+			add_flags<ENABLE_MULTIFLUID | ENABLE_DTADAPT | ENABLE_DENSITY_SUM>
+			).select_options(
+			RHODIFF == FERRARI, densitydiffusion<FERRARI>(),
+			RHODIFF == BREZZI, densitydiffusion<BREZZI>(),
+			RHODIFF == COLAGROSSI, densitydiffusion<COLAGROSSI>()
+		);
 	} else if (name == "AccuracyTest") {   // src/problems/AccuracyTest.cu:51-55
 		SETUP_FRAMEWORK(
 			viscosity<ARTVISC>,

@@ -101,6 +101,10 @@ class MultiGpuEngine:
         self.device = torch.device(device)
         self.is_cuda = self.device.type == "cuda"
         self.sp = problem.simparams
+        # formulation<SPH_HA> with SA walls (BiFluidPoiseuilleSA's set) takes the SA density-summation sequence as it is; slabs of it
+        # have never run
+        if self.sa and self.sp.sph_formulation == D.SPH_HA and world > 1:
+            raise NotImplementedError("SPH_HA with SA_BOUNDARY is built for a single domain")
         self.part = SlabPartition(problem, world)
         arrs = problem.copy_to_array()
         mask = self.part.local_mask(rank, arrs["hash"]) if world > 1 else np.ones(len(arrs["hash"]), dtype=bool)

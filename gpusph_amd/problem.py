@@ -925,6 +925,11 @@ class SABox(Problem):
         elif options == "Spheric2SA":
             sp.densitydiffusiontype = D.FERRARI
             sp.simflags = D.ENABLE_DTADAPT | D.ENABLE_GAMMA_QUADRATURE
+        elif options == "BiFluidPoiseuilleSA":      # SATwoFluidBox; its viscosity is part of the framework line
+            sp.sph_formulation = D.SPH_HA
+            sp.densitydiffusiontype = D.BREZZI
+            sp.densityDiffCoeff = 0.05
+            sp.simflags = D.ENABLE_MULTIFLUID | D.ENABLE_DTADAPT | D.ENABLE_DENSITY_SUM
         else:
             raise ValueError(options)
         self.options = options
@@ -942,9 +947,7 @@ class SABox(Problem):
         pp.gravity = (0.0, 0.0, -g)
         self.m_maxFall = self.H
         c0 = math.ceil(10.0 * math.sqrt(2.0 * g * self.H))
-        pp.add_fluid(1000.0)
-        pp.set_equation_of_state(0, 7.0, float(c0))
-        pp.set_kinematic_visc(0, 1.0e-2)
+        self._add_fluids(float(c0))
         # two boundary elements per lattice square inside the wider boundary radius: near a corner of the tank a particle
         # sees ~150 fluid + boundary neighbours, more than the default section: resize_neiblist(128+128, 64)
         # (src/problems/StillWaterSA.cu:54, src/ProblemCore.h:341-353)
@@ -952,6 +955,16 @@ class SABox(Problem):
         sp.neiblistsize = 256 + 64
         self.initialize()
         self.fill_parts()
+
+    def _add_fluids(self, c0):
+        pp = self.physparams
+        pp.add_fluid(1000.0)
+        pp.set_equation_of_state(0, 7.0, c0)
+        pp.set_kinematic_visc(0, 1.0e-2)
+
+    def _fluid_numbers(self, pos):
+        """fluid number of every particle (fluid, boundary element, vertex) at the global positions pos"""
+        return np.zeros(len(pos), dtype=np.uint16)
 
     def fill_parts(self):
         dp = self.m_deltap
@@ -1001,12 +1014,15 @@ class SABox(Problem):
         pos[:nf, :3] = fluid; pos[nf:nf + ns, :3] = spos; pos[nf + ns:, :3] = vpos
         pos[:nf + ns, 3] = rho0 * dp ** 3
         pos[nf + ns:, 3] = rho0 * dp ** 3 * frac
+        fnum = self._fluid_numbers(pos)
+        if fnum.any():      # masses are set up for fluid 0: scaled by rho0[f]/rho0[0] (src/problems/BiFluidPoiseuille.inc:232-235)
+            pos[:, 3] *= np.asarray(self.physparams.rho0)[fnum] / rho0
         vel = np.zeros((ntot, 4), dtype=np.float32)
         vel[:, 3] = self.initial_density(pos)
         tf = np.empty(ntot, dtype=np.uint16)
         tf[:nf] = D.PT_FLUID; tf[nf:nf + ns] = D.PT_BOUNDARY; tf[nf + ns:] = D.PT_VERTEX
         ids = np.arange(ntot, dtype=np.uint32)
-        info = make_particleinfo(tf, np.zeros(ntot, dtype=np.uint16), ids)
+        info = make_particleinfo(tf, (fnum << 12).astype(np.uint16), ids)
         self.parts = HostParticles(pos, vel, info)
         self.vertices = np.zeros((ntot, 4), dtype=np.uint32)
         self.vertices[nf:nf + ns, :3] = (tris + nf + ns).astype(np.uint32)          # vertex ids
@@ -1029,6 +1045,54 @@ class SABox(Problem):
         a = super().copy_to_array()
         a.update(vertices=self.vertices.copy(), boundelements=self.boundelements.copy(), gradgamma=self.gradgamma.copy())
         return a
+
+
+class SATwoFluidBox(SABox):
+    """SABox holding two fluids at rest, the heavier below: the closed-tank counterpart of the reference's BiFluidPoiseuilleSA
+    (src/problems/BiFluidPoiseuilleSA.cu through BiFluidPoiseuille.inc:45-59) with that problem's framework line: formulation<SPH_HA>,
+    rheology<NEWTONIAN>, turbulence_model<LAMINAR_FLOW>, computational_visc<DYNAMIC>, visc_model<MORRIS>, visc_average<HARMONIC>,
+    boundary<SA_BOUNDARY>, ENABLE_MULTIFLUID | ENABLE_DTADAPT | ENABLE_DENSITY_SUM, Brezzi diffusion by default (its run-time
+    option), densityDiffCoeff 0.05 (:69).  The fluids are those of its configuration 1 (:113-122): rho0 = 4000 / 1000, kinematic
+    viscosities in the ratio 4.  Fluid 0 lies below `interface` (default H/2, moved between two layers of the lattice), fluid 1
+    above; vertices and boundary elements carry the fluid number of their height (:217-227) and every mass is scaled by
+    rho0[f]/rho0[0] (:232-235).  The initial density is hydrostatic over the two layers.  The reference's problem is a channel
+    periodic in x and y read from a mesh file; this tank is closed (gravity along -z, SABox's walls, list sizes and smoothing)."""
+
+    def __init__(self, deltap=0.05, *, density_diffusion=D.BREZZI, interface=None, rho0=(4000.0, 1000.0), kinvisc=(1.0e-2, 2.5e-3), **kw):
+        if "options" in kw or "viscosity" in kw:
+            raise TypeError("SATwoFluidBox has BiFluidPoiseuilleSA's framework line: options and viscosity are not arguments")
+        self._rho0, self._kinvisc, self._interface_arg = tuple(rho0), tuple(kinvisc), interface
+        self._density_diffusion = density_diffusion
+        super().__init__(deltap, options="BiFluidPoiseuilleSA",
+                         viscosity=dict(rheologytype=D.NEWTONIAN, turbmodel=D.LAMINAR_FLOW, compvisc=D.DYNAMIC, viscmodel=D.MORRIS,
+                                        avgop=D.HARMONIC), **kw)
+        self.m_name = "SATwoFluidBox"
+
+    def _add_fluids(self, c0):
+        sp, pp = self.simparams, self.physparams
+        if self._density_diffusion not in (D.BREZZI, D.DENSITY_DIFFUSION_NONE):
+            raise ValueError("SATwoFluidBox: density diffusion is BREZZI or DENSITY_DIFFUSION_NONE")
+        sp.densitydiffusiontype = self._density_diffusion
+        for f, (rho, nu) in enumerate(zip(self._rho0, self._kinvisc)):
+            pp.add_fluid(rho)
+            pp.set_equation_of_state(f, 7.0, c0)
+            pp.set_kinematic_visc(f, nu)
+        dp = self.m_deltap
+        want = 0.5 * self.H if self._interface_arg is None else float(self._interface_arg)
+        self.interface = (math.floor(want / dp) + 0.5) * dp      # half way between two layers of the lattice
+
+    def _fluid_numbers(self, pos):
+        return np.where(pos[:, 2] < self.interface, 0, 1).astype(np.uint16)
+
+    def initial_density(self, pos_global):
+        pp = self.physparams
+        z = pos_global[:, 2]
+        top = np.clip(self.water_level - np.maximum(z, self.interface), 0.0, None)       # depth of fluid 1 above the point
+        bottom = np.clip(self.interface - z, 0.0, None)                                   # ... of fluid 0
+        pres = 9.81 * (pp.rho0[1] * top + pp.rho0[0] * bottom)
+        f = self._fluid_numbers(pos_global)
+        B, gam = np.asarray(pp.bcoeff)[f], np.asarray(pp.gammacoeff)[f]
+        return (np.power(1.0 + pres / B, 1.0 / gam) - 1.0).astype(np.float32)
 
 
 class SAProbeBox(SABox):

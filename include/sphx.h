@@ -255,7 +255,12 @@ int sphx_sa_body_pressure_forces(sphx_ctx *ctx, void *forces, void *rbforces, vo
  * entry point and by sphx_forces_basicstep_sa_keps alike, as a term of force.w before the division by gamma
  * (compute_density_diffusion, src/cuda/forces_kernel.def:1608-1705): fluid neighbours and boundary elements (rho and c of an element
  * from its row of `vel`, the pair's |grad gamma_as|) contribute, vertices do not; the coefficient is densityDiffCoeff.  FERRARI with
- * ENABLE_DENSITY_SUM, with open boundaries (the *_io entry points) and COLAGROSSI with SA_BOUNDARY answer SPHX_ERR_UNSUPPORTED. */
+ * ENABLE_DENSITY_SUM, with open boundaries (the *_io entry points) and COLAGROSSI with SA_BOUNDARY answer SPHX_ERR_UNSUPPORTED.
+ * SPH_HA (BiFluidPoiseuilleSA's set: several fluids, ENABLE_DENSITY_SUM with dynamic gamma, laminar, no or BREZZI diffusion, solid
+ * walls at rest) is built as well, on the list walkers: the Hu & Adams pressure terms here (forces_kernel.def:2289-2355,2395-2447),
+ * the volume-fraction weights of sphx_sa_density_sum (density_sum_kernel.cu:253-322) and the SPH_HA form of
+ * sphx_sa_compute_density_diffusion (forces_kernel.def:1786-1824: fluid and vertex neighbours); those two read their deltap argument
+ * then (deltap^3 is the reference volume of the volume fractions).  sphx_set_constants refuses every other SPH_HA + SA_BOUNDARY set. */
 int sphx_forces_basicstep_sa(sphx_ctx *ctx, void *forces, float *cfl, float *cflGamma,
 	const void *pos, const void *vel, const void *info, const uint32_t *hash, const uint32_t *cellStart, const uint16_t *neibsList,
 	const void *gGam, const void *boundElements, const void *vertPos0, const void *vertPos1, const void *vertPos2,
