@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import tiling_overflow_cases as toc
-from test_gpu_options import _check_neibs_and_forces, tiles_usable
+from forces_check import _check_neibs_and_forces, tiles_usable
 
 pytestmark = pytest.mark.gpu
 

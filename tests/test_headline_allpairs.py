@@ -20,8 +20,8 @@ The Colagrossi switch is decided by the last bits of P for pairs on its threshol
 within a few float32 ulp of the pressures) and their term is allowed either way -- they are counted and must stay rare."""
 import numpy as np
 import pytest
-from scipy.spatial import cKDTree
 
+import allpairs_ref as ap
 import oracle_lib as ol
 from gpusph_amd import defs as D
 from gpusph_amd.problem import DamBreak3D
@@ -43,13 +43,12 @@ def _state(viscosity=None, seed=5):
     return prob, sim, gp
 
 
-def _consts(sim):
-    p = sim.o.p
-    h = float(p.slength)
-    return dict(h=h, rho0=float(p.rho0[0]), B=float(p.bcoeff[0]), gam=float(p.gammacoeff[0]), c0=float(p.sscoeff[0]),
-                cpow=float(p.sspowercoeff[0]), g=np.array([p.gravity[0], p.gravity[1], p.gravity[2]], dtype=np.float64),
-                alpha=float(p.artvisccoeff), eps=float(p.epsartvisc), Dc=float(p.densityDiffCoeff),
-                fcoeff=105.0/(128.0*np.pi*h**5), R=float(p.influenceradius))
+_consts = ap.consts
+
+
+def _wendland_F(k):
+    """the headline kernel, as these two tests have always written it: F = (q - 2)^3 * 105 / (128 pi h^5)"""
+    return lambda r: (r/k["h"] - 2.0)**3*k["fcoeff"]
 
 
 def test_headline_option_set_equals_a_float64_all_pairs_evaluation():
@@ -65,48 +64,9 @@ def test_headline_option_set_equals_a_float64_all_pairs_evaluation():
     ptype = sim.info[:n, 0] & 7
     fluid, bound = ptype == D.PT_FLUID, ptype == D.PT_BOUNDARY
     assert fluid.sum() > 3000 and bound.sum() > 3000, (fluid.sum(), bound.sum())
-    m = sim.pos[:n, 3].astype(np.float64)
-    v = sim.vel[:n, :3].astype(np.float64)
-    ratio = sim.vel[:n, 3].astype(np.float64) + 1.0
-    rho = ratio*k["rho0"]
-    P = k["B"]*(ratio**k["gam"] - 1.0)
-    c = k["c0"]*ratio**k["cpow"]
-    # float32 rounding of P: what can move a pair across the Colagrossi threshold
-    Pulp = np.spacing(np.abs(P).astype(np.float32)).astype(np.float64)*4.0 + 1e-30
-
-    tree = cKDTree(gp)
-    acc = np.zeros((n, 3)); drdt = np.zeros(n); amb = np.zeros(n)
-    pairs = ambiguous = 0
-    nbs_all = tree.query_ball_point(gp, k["R"]*(1 - 1e-7))
-    for i in range(n):
-        nb = np.array([j for j in nbs_all[i] if j != i], dtype=np.int64)
-        if bound[i]:
-            nb = nb[fluid[nb]]                     # DYN boundary particles list fluid neighbours only
-        if not len(nb):
-            continue
-        d = gp[i] - gp[nb]
-        r2 = (d*d).sum(axis=1)
-        r = np.sqrt(r2)
-        F = (r/k["h"] - 2.0)**3*k["fcoeff"]
-        vr = ((v[i] - v[nb])*d).sum(axis=1)
-        mF = m[nb]*F
-        cont = mF*vr
-        nf = fluid[nb]
-        margin = np.abs(P[i] - P[nb]) - np.abs((d @ k["g"])*rho[i])
-        dterm = k["Dc"]*k["c0"]*(rho[nb]/rho[i] - 1.0)*mF
-        on = nf & (margin >= 0.0)
-        edge = nf & (np.abs(margin) <= Pulp[i] + Pulp[nb] + 1e-6*np.abs((d @ k["g"])*rho[i]))
-        drdt[i] = cont.sum() - dterm[on & ~edge].sum()
-        # threshold pairs: counted either way
-        amb[i] = np.abs(dterm[edge]).sum()
-        drdt[i] -= 0.5*dterm[edge].sum()
-        pairs += int(nf.sum()); ambiguous += int(edge.sum())
-        if fluid[i]:
-            pg = P[i]/rho[i]**2 + P[nb]/rho[nb]**2
-            visc = np.where(vr < 0.0, vr*k["h"]*k["alpha"]*(c[i] + c[nb])/((r2 + k["eps"])*(rho[i] + rho[nb])), 0.0)
-            acc[i] = ((visc - pg)*mF) @ d + k["g"]
-    drt = drdt/k["rho0"]
-    amb = 0.5*amb/k["rho0"]
+    # the float64 all-pairs sums (tests/allpairs_ref.py; the kernel function is its parameter)
+    ref = ap.momentum_continuity(sim, gp, k, _wendland_F(k))
+    acc, drt, amb, pairs, ambiguous = ref["acc"], ref["drt"], ref["amb"], ref["pairs"], ref["ambiguous"]
 
     # momentum equation: every fluid particle; walls without force feedback carry no acceleration
     ascale = np.abs(acc[fluid]).max()
@@ -126,39 +86,6 @@ def test_headline_option_set_equals_a_float64_all_pairs_evaluation():
     assert np.abs(drt[bound]).max() > 0.05*dscale
 
 
-def _tau_all_pairs(sim, gp, k, smag, ksps):
-    n = sim.n
-    m = sim.pos[:n, 3].astype(np.float64)
-    v = sim.vel[:n, :3].astype(np.float64)
-    rho = (sim.vel[:n, 3].astype(np.float64) + 1.0)*k["rho0"]
-    ptype = sim.info[:n, 0] & 7
-    bound = ptype == D.PT_BOUNDARY
-    fluid = ptype == D.PT_FLUID
-    tree = cKDTree(gp)
-    tau = np.zeros((n, 6)); nu = np.zeros(n)
-    nbs_all = tree.query_ball_point(gp, k["R"]*(1 - 1e-7))
-    for i in range(n):
-        nb = np.array([j for j in nbs_all[i] if j != i], dtype=np.int64)
-        if bound[i]:
-            nb = nb[fluid[nb]]
-        if not len(nb):
-            continue
-        d = gp[i] - gp[nb]
-        r = np.sqrt((d*d).sum(axis=1))
-        w = (r/k["h"] - 2.0)**3*k["fcoeff"]*m[nb]/rho[nb]
-        dv = -((v[i] - v[nb])[:, :, None]*(d*w[:, None])[:, None, :]).sum(axis=0)     # dv[a][b] = d v_a / d x_b
-        xx, yy, zz = dv[0, 0], dv[1, 1], dv[2, 2]
-        xy, xz, yz = dv[0, 1] + dv[1, 0], dv[0, 2] + dv[2, 0], dv[1, 2] + dv[2, 1]
-        S2 = 2.0*(xx*xx + yy*yy + zz*zz) + xy*xy + xz*xz + yz*yz
-        S = np.sqrt(S2)
-        nu[i] = smag*S
-        divu = (2.0/3.0)*nu[i]*(xx + yy + zz)
-        bl = ksps*S2
-        tau[i] = [(2*nu[i]*xx - divu - bl)/rho[i], nu[i]*xy/rho[i], nu[i]*xz/rho[i],
-                  (2*nu[i]*yy - divu - bl)/rho[i], nu[i]*yz/rho[i], (2*nu[i]*zz - divu - bl)/rho[i]]
-    return tau, nu
-
-
 def test_sps_stress_tensor_equals_a_float64_all_pairs_evaluation():
     prob, sim, gp = _state(viscosity="SPSVISC", seed=9)
     n = sim.n
@@ -169,7 +96,7 @@ def test_sps_stress_tensor_equals_a_float64_all_pairs_evaluation():
     dp = float(prob.m_deltap)
     assert smag == pytest.approx((0.12*dp)**2, rel=1e-6) and ksps == pytest.approx((2*0.0066/3)*dp*dp, rel=1e-6)   # GPUSPH.cc:1542-1554
     tau, tv = sim.o.sps(sim.pos, sim.vel, sim.info, sim.hash, sim.cs, sim.nl, n, n)
-    ref, nu = _tau_all_pairs(sim, gp, k, smag, ksps)
+    ref, nu = ap.tau_all_pairs(sim, gp, k, smag, ksps, _wendland_F(k))
     scale = np.abs(ref).max(axis=0)
     assert (scale > 0).all() and np.abs(nu).max() > 0
     assert (np.abs(tau[:n] - ref) <= 2e-5*scale.max()).all(), np.abs(tau[:n] - ref).max(axis=0)/scale.max()
@@ -187,20 +114,8 @@ def test_sps_stress_tensor_equals_a_float64_all_pairs_evaluation():
     f_0 = sim.o.forces(sim.pos, sim.vel, sim.info, sim.hash, sim.cs, sim.nl, n, tau=np.zeros_like(tau))[0][:n].astype(np.float64)
     term = f_tau[:, :3] - f_0[:, :3]
     assert np.array_equal(f_tau[:, 3], f_0[:, 3])
-    T = np.zeros((n, 3, 3))
-    t64 = tau[:n].astype(np.float64)
-    T[:, 0, 0], T[:, 0, 1], T[:, 0, 2], T[:, 1, 1], T[:, 1, 2], T[:, 2, 2] = t64.T
-    T[:, 1, 0], T[:, 2, 0], T[:, 2, 1] = T[:, 0, 1], T[:, 0, 2], T[:, 1, 2]
-    m = sim.pos[:n, 3].astype(np.float64)
     fluid = (sim.info[:n, 0] & 7) == D.PT_FLUID
-    tree = cKDTree(gp)
-    want = np.zeros((n, 3))
-    for i in np.where(fluid)[0]:
-        nb = np.array([j for j in tree.query_ball_point(gp[i], k["R"]*(1 - 1e-7)) if j != i], dtype=np.int64)
-        d = gp[i] - gp[nb]
-        r = np.sqrt((d*d).sum(axis=1))
-        mF = m[nb]*(r/k["h"] - 2.0)**3*k["fcoeff"]
-        want[i] = np.einsum("j,jab,jb->a", mF, T[i][None] + T[nb], d)
+    want = ap.sps_divergence(sim, gp, k, tau, _wendland_F(k))
     ts = np.abs(want).max()
     fs = np.abs(f_0[fluid, :3]).max()
     assert ts > 0.1*fs
