@@ -90,7 +90,7 @@ class TimestepEngine(MultiGpuEngine):
         self._rows_for = None      # the velocity buffer may be rewritten behind torch's back (multigpu.py, _rows_for)
         n = self.n_local
         self.k.filter(int(filtertype), self.vel2, self.pos, self.vel, self.info, self.hash, self.cellStart, self.neibslist, n, n)
-        self.vel, self.vel2 = self.vel2, self.vel
+        self._swap("vel")
 
     # ------------------------------------------------------------------ post-processing (before writes)
     def postprocess(self, pptype, normals=False):
@@ -138,9 +138,8 @@ class TimestepEngine(MultiGpuEngine):
         if self.sa:      # INTEGRATE_GAMMA of the new state (RepackingIntegrator.cc:386-405); gamma by quadrature only
             self.k.sa_integrate_gamma(self.gradgamma2, self.gradgamma, self.pos2, self.boundelements, self.vertpos, self.info, self.hash,
                                       self.cellStart, self.neibslist, self.n_local, self.n_local)
-            self.gradgamma, self.gradgamma2 = self.gradgamma2, self.gradgamma
-        self.pos, self.pos2 = self.pos2, self.pos
-        self.vel, self.vel2 = self.vel2, self.vel
+        # what a repacking iteration wrote a new copy of: no other state buffer moves (BUFFERS in multigpu.py)
+        self._swap(*(("pos", "vel", "gradgamma") if self.sa else ("pos", "vel")))
         self.k.time_advance(self.d_t, self.d_dt)
         self.d_dt, self.d_dt_next = self.d_dt_next, self.d_dt
         self.iterations += 1
@@ -164,7 +163,7 @@ class TimestepEngine(MultiGpuEngine):
         # the restart below re-initialises velocities and densities only.  Option sets that carry more evolved state would need
         # what a run resumed from the repack file re-initialises as well (volumes: GPUSPH.cc:495; internal energy, k-epsilon
         # fields, the gamma of dynamic-gamma SA runs): refused rather than left half reset
-        if self.grenier or self.energy_on or self.keps or (self.sa and getattr(self, "sa_dynamic_gamma", False)):
+        if any(b.evolves(self) for b in self._bufs if b.name not in ("pos", "vel")):
             raise ValueError("repack(reset=True) is built for runs whose evolved state is positions, velocities and densities: "
                              "not with SPH_GRENIER volumes, internal energy, k-epsilon or dynamic gamma (use reset=False and "
                              "re-initialise those buffers)")
@@ -206,27 +205,17 @@ class TimestepEngine(MultiGpuEngine):
         (src/writers/HotFile.cc:143): POS_GLOBAL, POS, VEL, INFO, HASH, + BOUNDELEMENTS, VERTICES, GRADGAMMA with
         SA_BOUNDARY, SPS_TURBVISC with SPS, EFFVISC with a generalized Newtonian rheology, VOLUME and SIGMA with
         SPH_GRENIER, INTERNAL_ENERGY with its flag (GPUSPH::allocateGlobalHostBuffers, GPUSPH.cc:868-941)"""
-        return (5 + (3 if self.sa else 0) + (1 if self.sps else 0) + (1 if self.effvisc_on else 0)
-                + (2 if self.grenier else 0) + (1 if self.energy_on else 0) + (4 if self.keps else 0))     # TKE, EPSILON, TURBVISC, EULERVEL
+        return 5 + len(self._hot_rows()) + (1 if self.sps else 0) + (1 if self.effvisc_on else 0) + (1 if self.grenier else 0)      # (SIGMA)
 
     def _hot_extra(self):
         """the option-dependent particle property buffers a HotFile stores beside pos/vel/info/hash: name -> device tensor"""
-        ex = {}
-        if self.energy_on:
-            ex["energy"] = self.energy
-        if self.sa:
-            ex.update(boundelements=self.boundelements, gradgamma=self.gradgamma, vertices=self.vertices)
-        if self.keps:
-            ex.update(self.ke)
-        if self.grenier:
-            ex["vol"] = self.vol
-        return ex
+        return {k: t for k, t, _ in self._hot_rows()}
 
     def save_hotfile(self, path):
         """HotFile::save of the current state (src/writers/HotFile.cc:86-118); readable by GPUSPH --resume and by
         the reference's scripts/hotdiff.py.  One body record per body, from the LIVE kinematic data (writeBody :285-340)."""
         from . import hotfile
-        if getattr(self, "granular", False):      # BUFFER_EFFPRES is state a resumed run needs; its place in the file is not built
+        if self.granular:      # BUFFER_EFFPRES is state a resumed run needs; its place in the file is not built
             raise NotImplementedError("HotFile checkpoints of a run with the GRANULAR rheology are not built")
         st = self.download()
         bodies = []
@@ -263,7 +252,7 @@ class TimestepEngine(MultiGpuEngine):
         the kinematic data of the moving bodies (readBody) and the centres of rotation of both engines."""
         self._rows_for = None      # the velocity buffer may be rewritten behind torch's back (multigpu.py, _rows_for)
         from . import hotfile
-        if getattr(self, "granular", False):
+        if self.granular:
             raise NotImplementedError("HotFile checkpoints of a run with the GRANULAR rheology are not built")
         self._surface_for = None
         hf = hotfile.read_hotfile(path)
@@ -279,10 +268,10 @@ class TimestepEngine(MultiGpuEngine):
         self.pos[:n] = torch.from_numpy(a["pos"]).to(dev); self.vel[:n] = torch.from_numpy(a["vel"]).to(dev)
         self.info[:n] = torch.from_numpy(a["info"].view(np.int16)).to(dev)
         self.hash[:n] = torch.from_numpy(a["hash"].view(np.int32)).to(dev)
-        for k, t in self._hot_extra().items():
+        for k, t, view in self._hot_rows():
             if k not in a:
                 raise capi.SphxError("HotFile lacks the '%s' buffer this option set evolves" % k)
-            t[:n] = torch.from_numpy(a[k].view(np.int32) if k == "vertices" else a[k]).to(dev)
+            t[:n] = torch.from_numpy(a[k].view(view) if view else a[k]).to(dev)
         self.iterations = int(hf["iterations"])
         self.dt = float(np.float32(hf["dt"]))
         self.d_dt.fill_(self.dt); self.d_dt_next.fill_(self.dt)

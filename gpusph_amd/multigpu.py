@@ -24,10 +24,72 @@ What it mirrors in GPUSPH (paths relative to the GPUSPH tree) and what it change
 Results are bit-identical to the single-device run (same per-particle neighbour order and arithmetic).
 """
 import os
+from collections import namedtuple
+from types import SimpleNamespace
 import numpy as np
 import torch
 
 from . import defs as D
+
+# ---------------------------------------------------------------------- the particle-state buffers of a step
+# One row per buffer that holds one value per particle and exists twice: engine.<name> and engine.<name>2.  Allocation, the
+# re-sort, the halo state, the renaming at the end of a step, download_internal and the HotFile set are loops over this table: a
+# new property buffer is a new row (DESIGN.md section 7), and what a row leaves out it leaves out on purpose.
+#   has      which option sets have the buffer (a predicate on the engine)
+#   dtype, row   of the device tensors: (allocated,) + row; a dict of rows for `ke`, which is a dict of tensors in that order
+#   init     ARRAY: problem.copy_to_array()[name] (`view`: the dtype the host array is read or written as); FILL: stays at `fill`;
+#            else the engine method (arrs, mask, n0) that sets it up once everything is allocated.  Both copies start from `fill`.
+#   resort   GATHER: gather_rows into the second copy after every sort, then renamed; REORDER: inside the reorder pass itself
+#   halo     exchanged by _update_segments_and_halo, in table order behind pos, vel, info and hash
+#   stepped  a step writes the new state into the second copy, renamed at the end of the step (_state_of tells the two states apart);
+#            where false the second copy is scratch of the re-sort only
+#   evolves  a step integrates it from its own last value: repack(reset=True), which restarts positions, velocities and
+#            densities only, refuses option sets that have such a buffer beyond pos and vel
+#   hot      stored in a HotFile under its name (ke: its fields' names)
+#   download returned by download_internal under its name (ke: its fields' names)
+# The order is that of the gathers of a re-sort.  The halo state of the parent had vol and energy ahead of the SA buffers; the
+# library refuses ENABLE_INTERNAL_ENERGY and SPH_GRENIER with SA_BOUNDARY and with each other (energy.hip, sphx_set_constants), so
+# no run has two of the three and both ranks of every run see the order they always saw.
+Buf = namedtuple("Buf", "name has dtype row view fill init resort halo stepped evolves hot download")
+ARRAY, FILL, GATHER, REORDER = "array", "fill", "gather", "reorder"
+_f32, _i32 = torch.float32, torch.int32
+_yes, _no = (lambda e: True), (lambda e: False)
+BUFFERS = (
+    Buf("pos", _yes, _f32, (4,), None, 0, ARRAY, REORDER, True, _yes, _yes, False, True),
+    Buf("vel", _yes, _f32, (4,), None, 0, ARRAY, REORDER, True, _yes, _yes, False, True),
+    # SA_BOUNDARY: BUFFER_VERTICES (uint4: int32 on the device, uint32 in the host arrays and in a HotFile), BUFFER_BOUNDELEMENTS,
+    # BUFFER_GRADGAMMA (float4), the optional arrays of reorderDataAndFindCellStart (src/cuda/buildneibs.cu:263-311).
+    # download_internal leaves the vertices out.
+    Buf("vertices", lambda e: e.sa, _i32, (4,), np.int32, 0, ARRAY, GATHER, True, _no, _no, True, False),
+    # with bodies of prescribed motion the Euler step turns the normals of the moving segments and vertices: boundelements2 is
+    # then the state n* / n+1 (PredictorCorrectorIntegrator.cc:408-418); a function of time, which repack(reset=True) lets pass
+    Buf("boundelements", lambda e: e.sa, _f32, (4,), None, 0, ARRAY, GATHER, True, lambda e: e.sa_moving, _no, True, True),
+    # gamma by quadrature is recomputed from the positions in every step, dynamic gamma is integrated
+    Buf("gradgamma", lambda e: e.sa, _f32, (4,), None, 0, ARRAY, GATHER, True, _yes, lambda e: e.sa_dynamic_gamma, True, True),
+    # open boundaries: BUFFER_EULERVEL (the halo's vertices and segments enter the forces with theirs) and BUFFER_NEXTID; neither is
+    # in a HotFile or in download_internal
+    Buf("eulervel", lambda e: e.io, _f32, (4,), None, 0, FILL, GATHER, True, _yes, _yes, False, False),
+    Buf("next_ids", lambda e: e.io, _i32, (), None, -1, "_init_next_ids", GATHER, False, _no, _no, False, False),
+    # ENABLE_INTERNAL_ENERGY: BUFFER_INTERNAL_ENERGY starts from zero (init_internal_energy)
+    Buf("energy", lambda e: e.energy_on, _f32, (), None, 0, FILL, GATHER, True, _yes, _yes, True, True),
+    # turbulence<KEPSILON>: BUFFER_TKE / EPSILON / TURBVISC / EULERVEL as one dict in that order; its eulervel is not the open
+    # boundaries' (open boundaries refuse k-epsilon)
+    Buf("ke", lambda e: e.keps, _f32, dict(tke=(), eps=(), turbvisc=(), eulervel=(4,)), None, 0, "_init_keps", GATHER, True, _yes, _yes,
+        True, True),
+    # SPH_GRENIER: BUFFER_VOLUME; the halo copies integrate theirs from the exchanged forces
+    Buf("vol", lambda e: e.grenier, _f32, (4,), None, 0, "_init_volume", GATHER, True, _yes, _yes, True, True),
+    # GRANULAR: BUFFER_EFFPRES starts from the problem's field and every solve starts from the last one's result, in place.  It is
+    # neither halo state nor in a HotFile: runs on several domains and checkpoints of GRANULAR are refused with their messages
+    Buf("effpres", lambda e: e.granular, _f32, (), None, 0, ARRAY, GATHER, False, _no, _no, False, True),
+)
+
+
+def _tensors(v):
+    return list(v.values()) if isinstance(v, dict) else [v]
+
+
+def _items(name, v):
+    return list(v.items()) if isinstance(v, dict) else [(name, v)]
 
 
 class SlabPartition:
@@ -141,6 +203,31 @@ class MultiGpuEngine:
             self.transport = transport
         dev, A = self.device, self.alloc
         f32, i32, i16 = torch.float32, torch.int32, torch.int16
+        # SA_BOUNDARY: dynamic gamma (no ENABLE_GAMMA_QUADRATURE) or gamma by quadrature, density summation or continuity equation
+        self.sa_dynamic_gamma = self.sa and not (self.sp.simflags & D.ENABLE_GAMMA_QUADRATURE)
+        self.sa_density_sum = self.sa and bool(self.sp.simflags & D.ENABLE_DENSITY_SUM)
+        # SA open boundaries (ENABLE_INLET_OUTLET): the particle count grows inside the allocation.  The density summation form, a
+        # rebuild in every iteration (the reference's open-boundary problems set buildneibsfreq = 1: a released particle exists for
+        # the lists from the next rebuild on).  See _sa_post_euler_io.
+        self.io = self.sa and bool(self.sp.simflags & D.ENABLE_INLET_OUTLET)
+        # SA bodies with prescribed motion: BUFFER_BOUNDELEMENTS is a state buffer (BUFFERS)
+        self.sa_moving = self.sa and bool(self.sp.simflags & D.ENABLE_MOVING_BODIES)
+        if self.sa_moving and self.keps:
+            raise NotImplementedError("SA bodies with prescribed motion: not together with k-epsilon")
+        if self.io:
+            if not self.sa_density_sum or self.keps or self.sp.buildneibsfreq != 1:
+                raise NotImplementedError("open boundaries are built for the density summation form without k-epsilon, buildneibsfreq = 1")
+            if not hasattr(problem, "impose_open_boundaries"):
+                raise ValueError("a problem with ENABLE_INLET_OUTLET needs impose_open_boundaries (its imposeBoundaryConditionHost)")
+        # GRANULAR: BUFFER_EFFPRES is solved at initialisation, after the predictor and after the corrector (_solve_effpres); single
+        # domain: the exchange of the pressure per Jacobi iteration is not built
+        self.granular = self.sp.rheologytype == D.GRANULAR
+        if self.granular and world > 1:
+            raise NotImplementedError("the GRANULAR rheology is built for a single domain")
+        self.energy_on = bool(self.sp.simflags & D.ENABLE_INTERNAL_ENERGY)
+        self._bufs = tuple(b for b in BUFFERS if b.has(self))
+        self._resorted = tuple(b.name for b in self._bufs if b.resort)
+        self._stepped = tuple(b.name for b in self._bufs if b.stepped(self))
 
         def up(a, dtype, shape):
             t = torch.zeros(shape, dtype=dtype, device=dev)
@@ -148,8 +235,14 @@ class MultiGpuEngine:
             return t
 
         self.n_local = n0
-        self.pos = up(arrs["pos"], f32, (A, 4)); self.vel = up(arrs["vel"], f32, (A, 4))
-        self.pos2 = torch.zeros_like(self.pos); self.vel2 = torch.zeros_like(self.vel)
+        for b in self._bufs:         # both copies of every state buffer, at their fill value
+            def full(row):
+                return torch.full((A,) + row, b.fill, dtype=b.dtype, device=dev)
+            for name in (b.name, b.name + "2"):
+                setattr(self, name, {k: full(r) for k, r in b.row.items()} if isinstance(b.row, dict) else full(b.row))
+            if b.init == ARRAY:
+                a = arrs[b.name]
+                getattr(self, b.name)[:n0] = torch.from_numpy((a.view(b.view) if b.view else a)[mask]).to(dev)
         self.info = up(arrs["info"].view(np.int16), i16, (A, 4))
         self.hash = up(arrs["hash"].view(np.int32), i32, (A,))
         self.partindex = torch.zeros(A, dtype=i32, device=dev)
@@ -200,79 +293,31 @@ class MultiGpuEngine:
         self.turbvisc = torch.zeros(A, dtype=f32, device=dev) if self.sps else None      # BUFFER_SPS_TURBVISC
         # ENABLE_XSPH: BUFFER_XSPH, written by every forces pass for the fluid particles, read by the Euler steps
         self.xsph = torch.zeros((A, 4), dtype=f32, device=dev) if (self.sp.simflags & D.ENABLE_XSPH) else None
-        # SA_BOUNDARY: BUFFER_VERTICES (uint4), BUFFER_BOUNDELEMENTS, BUFFER_GRADGAMMA (float4) travel through the re-sort like
-        # pos/vel; BUFFER_VERTPOS (3 x float2) is written by the list build
-        if self.sa:
-            self.vertices = up(arrs["vertices"].view(np.int32), i32, (A, 4)); self.vertices2 = torch.zeros_like(self.vertices)
-            self.boundelements = up(arrs["boundelements"], f32, (A, 4)); self.boundelements2 = torch.zeros_like(self.boundelements)
-            self.gradgamma = up(arrs["gradgamma"], f32, (A, 4)); self.gradgamma2 = torch.zeros_like(self.gradgamma)
+        # what the option sets hold beside their state buffers
+        if self.sa:      # BUFFER_VERTPOS (3 x float2) is written by the list build
             self.vertpos = [torch.zeros((A, 2), dtype=f32, device=dev) for _ in range(3)]
-            # dynamic gamma (no ENABLE_GAMMA_QUADRATURE): BUFFER_CFL_GAMMA, per particle and, behind round_up(n, 4), per block
-            self.sa_dynamic_gamma = not (self.sp.simflags & D.ENABLE_GAMMA_QUADRATURE)
-            self.sa_density_sum = bool(self.sp.simflags & D.ENABLE_DENSITY_SUM)
+            # dynamic gamma: BUFFER_CFL_GAMMA, per particle and, behind round_up(n, 4), per block
             self.cfl_gamma = (torch.zeros(A + 4 + self.cfl.numel(), dtype=f32, device=dev) if self.sa_dynamic_gamma else None)
-        # SA open boundaries (ENABLE_INLET_OUTLET): BUFFER_EULERVEL (double buffered) and BUFFER_NEXTID travel through the re-sort,
-        # IOwaterdepth is one uint per open boundary, the particle count grows inside the allocation.  The density
-        # summation form, a rebuild in every iteration (the reference's open-boundary problems set buildneibsfreq = 1: a released
-        # particle exists for the lists from the next rebuild on).  See _sa_post_euler_io.
-        self.io = self.sa and bool(self.sp.simflags & D.ENABLE_INLET_OUTLET)
-        # SA bodies with prescribed motion: BUFFER_BOUNDELEMENTS is a state buffer (the Euler step turns the normals of the moving
-        # segments and vertices), boundelements2 holds it for the state n* / n+1 (PredictorCorrectorIntegrator.cc:408-418)
-        self.sa_moving = self.sa and bool(self.sp.simflags & D.ENABLE_MOVING_BODIES)
-        if self.sa_moving and self.keps:
-            raise NotImplementedError("SA bodies with prescribed motion: not together with k-epsilon")
-        if self.io:
-            if not self.sa_density_sum or self.keps or self.sp.buildneibsfreq != 1:
-                raise NotImplementedError("open boundaries are built for the density summation form without k-epsilon, buildneibsfreq = 1")
-            if not hasattr(problem, "impose_open_boundaries"):
-                raise ValueError("a problem with ENABLE_INLET_OUTLET needs impose_open_boundaries (its imposeBoundaryConditionHost)")
-            self.eulervel = torch.zeros((A, 4), dtype=f32, device=dev); self.eulervel2 = torch.zeros_like(self.eulervel)
-            # initializeNextIDs (src/GPUSPH.cc:1256-1302): the vertices of open boundaries get totParticles, totParticles + 1, ...
-            # in particle order; nobody else has one
-            flags = arrs["info"][:, 0]
-            openv = ((flags & 7) == D.PT_VERTEX) & ((flags & (D.FG_INLET | D.FG_OUTLET)) != 0)
-            nid = np.full(len(flags), 0xFFFFFFFF, dtype=np.uint32)
-            nid[openv] = len(flags) + np.arange(int(openv.sum()), dtype=np.uint32)
-            self.num_open_vertices = int(openv.sum())
-            self.next_ids = torch.full((A,), -1, dtype=i32, device=dev)
-            self.next_ids[:n0] = torch.from_numpy(nid.view(np.int32)[mask]).to(dev)
-            self.next_ids2 = torch.full((A,), -1, dtype=i32, device=dev)
+        if self.io:      # IOwaterdepth is one uint per open boundary
             self.water_depth_on = bool(self.sp.simflags & D.ENABLE_WATER_DEPTH)
             self.iowaterdepth = torch.zeros(max(int(problem.num_open_boundaries), 1), dtype=i32, device=dev) if self.water_depth_on else None
             self.io_count = torch.zeros(1, dtype=i32, device=dev)         # newNumParticles of the vertex pass
             self.io_created = self.io_removed = 0
-        # turbulence<KEPSILON>: BUFFER_TKE / EPSILON / TURBVISC / EULERVEL are particle properties (double buffered, re-sorted);
-        # ProblemCore::init_keps and init_turbvisc (src/ProblemCore.cc:1623-1659) give the uniform initial state; BUFFER_DKDE and
-        # BUFFER_CFL_KEPS are outputs of the forces passes
-        if self.keps:
-            k0, e0, nut0 = problem.init_keps()
-            self.ke = dict(tke=torch.full((A,), k0, dtype=f32, device=dev), eps=torch.full((A,), e0, dtype=f32, device=dev),
-                           turbvisc=torch.full((A,), nut0, dtype=f32, device=dev), eulervel=torch.zeros((A, 4), dtype=f32, device=dev))
-            self.ke2 = {k: torch.zeros_like(v) for k, v in self.ke.items()}
+        if self.keps:    # BUFFER_DKDE and BUFFER_CFL_KEPS are outputs of the forces passes
             self.dkde = torch.zeros((A, 3), dtype=f32, device=dev)
             self.cfl_keps = torch.zeros_like(self.cfl)
         self.effvisc = torch.zeros(A, dtype=f32, device=dev) if self.effvisc_on else None      # BUFFER_EFFVISC
-        # GRANULAR: BUFFER_EFFPRES is particle state (re-sorted, double buffered for that); it starts from the problem's field and
-        # every solve starts from the last one's result.  Solved at initialisation, after the predictor and after the corrector
-        # (_solve_effpres); single domain: the exchange of the pressure per Jacobi iteration is not built
-        self.granular = self.sp.rheologytype == D.GRANULAR
         if self.granular:
-            if world > 1:
-                raise NotImplementedError("the GRANULAR rheology is built for a single domain")
-            self.effpres = up(arrs["effpres"], f32, (A,)); self.effpres2 = torch.zeros_like(self.effpres)
             self.jacobi_iterations = {}      # phase ("init", "predictor", "corrector") -> h_jacobiCounter of its last solve
             self.jacobi_last = {}            # ... -> (backward error, residual) its stop test saw
             self.jacobi_max_iterations = 0   # the largest counter of any solve so far
-        # ENABLE_INTERNAL_ENERGY: BUFFER_INTERNAL_ENERGY (double buffered, re-sorted; starts from zero: init_internal_energy) and its rate
-        self.energy_on = bool(self.sp.simflags & D.ENABLE_INTERNAL_ENERGY)
         if self.energy_on:
-            self.energy = torch.zeros(A, dtype=f32, device=dev); self.energy2 = torch.zeros_like(self.energy)
-            self.dedt = torch.zeros(A, dtype=f32, device=dev)
-        # SPH_GRENIER: BUFFER_VOLUME (double buffered like pos/vel, travels through the re-sort) and BUFFER_SIGMA
+            self.dedt = torch.zeros(A, dtype=f32, device=dev)      # the rate of BUFFER_INTERNAL_ENERGY
         if self.grenier:
-            self.vol = torch.zeros((A, 4), dtype=f32, device=dev); self.vol2 = torch.zeros_like(self.vol)
-            self.sigma = torch.zeros(A, dtype=f32, device=dev)
-            self.k.init_volume(self.vol, self.pos, self.vel, self.info, n0)      # GPUSPH.cc:495-496
+            self.sigma = torch.zeros(A, dtype=f32, device=dev)     # BUFFER_SIGMA
+        for b in self._bufs:         # the buffers that a call sets up
+            if b.init not in (ARRAY, FILL):
+                getattr(self, b.init)(arrs, mask, n0)
         self.filters = []            # [(FilterType, frequency)]
         # bodies with prescribed motion: every rank runs the same host kinematics (the callback is a pure function of time)
         self.bodies = None
@@ -280,6 +325,46 @@ class MultiGpuEngine:
             from .bodies import MovingBodies
             self.bodies = MovingBodies(problem, problem.rb_cg_global)
         self.t_host = 0.0
+
+    # ------------------------------------------------------------------ state buffers (BUFFERS)
+    def _init_next_ids(self, arrs, mask, n0):
+        """initializeNextIDs (src/GPUSPH.cc:1256-1302): the vertices of open boundaries get totParticles, totParticles + 1, ... in
+        particle order; nobody else has one"""
+        flags = arrs["info"][:, 0]
+        openv = ((flags & 7) == D.PT_VERTEX) & ((flags & (D.FG_INLET | D.FG_OUTLET)) != 0)
+        nid = np.full(len(flags), 0xFFFFFFFF, dtype=np.uint32)
+        nid[openv] = len(flags) + np.arange(int(openv.sum()), dtype=np.uint32)
+        self.num_open_vertices = int(openv.sum())
+        self.next_ids[:n0] = torch.from_numpy(nid.view(np.int32)[mask]).to(self.device)
+
+    def _init_keps(self, arrs, mask, n0):
+        """ProblemCore::init_keps and init_turbvisc (src/ProblemCore.cc:1623-1659): the uniform initial state"""
+        for t, v in zip(_tensors(self.ke), self.problem.init_keps()):      # k, epsilon, nu_t; the Eulerian velocity stays zero
+            t.fill_(v)
+
+    def _init_volume(self, arrs, mask, n0):
+        self.k.init_volume(self.vol, self.pos, self.vel, self.info, n0)      # GPUSPH.cc:495-496
+
+    def _swap(self, *names):
+        """rename <name> <-> <name>2"""
+        for name in names:
+            cur, other = getattr(self, name), getattr(self, name + "2")
+            setattr(self, name, other); setattr(self, name + "2", cur)
+
+    def _state_of(self, pos):
+        """The state buffers that go with `pos`: those of the current state for self.pos, for anything else (self.pos2: n* and
+        n+1 while a step is under way) the copy that the step writes, where it writes one."""
+        new = pos is not self.pos
+        return SimpleNamespace(**{b.name: getattr(self, b.name + "2" if new and b.name in self._stepped else b.name) for b in self._bufs})
+
+    def halo_state(self):
+        """what _update_segments_and_halo exchanges after a re-sort, in the order both ranks share"""
+        state = [t for b in self._bufs if b.halo for t in _tensors(getattr(self, b.name))]
+        return state[:2] + [self.info, self.hash] + state[2:]
+
+    def _hot_rows(self):
+        """(HotFile key, device tensor, dtype of the host array or None) of the option-dependent buffers a HotFile stores"""
+        return [(k, t, b.view) for b in self._bufs if b.hot for k, t in _items(b.name, getattr(self, b.name))]
 
     # ------------------------------------------------------------------ exchange
     def _neighbours(self):
@@ -308,31 +393,11 @@ class MultiGpuEngine:
         K.memset(self.cellEnd, 0xFF)
         K.reorder(self.segment_start if self.world > 1 else None, self.cellStart, self.cellEnd, self.pos2, self.vel2,
                   self.pos, self.vel, self.info, self.hash, self.partindex, n, self.new_num)
-        self.pos, self.pos2 = self.pos2, self.pos
-        self.vel, self.vel2 = self.vel2, self.vel
-        if self.sa:      # the optional arrays of reorderDataAndFindCellStart (src/cuda/buildneibs.cu:263-311)
-            for name in ("vertices", "boundelements", "gradgamma"):
-                src, dst = getattr(self, name), getattr(self, name + "2")
-                K.gather_rows(dst, src, self.partindex, n)
-                setattr(self, name, dst); setattr(self, name + "2", src)
-        if self.io:      # BUFFER_EULERVEL and BUFFER_NEXTID are particle state too
-            for name in ("eulervel", "next_ids"):
-                src, dst = getattr(self, name), getattr(self, name + "2")
-                K.gather_rows(dst, src, self.partindex, n)
-                setattr(self, name, dst); setattr(self, name + "2", src)
-        if self.energy_on:
-            K.gather_rows(self.energy2, self.energy, self.partindex, n)
-            self.energy, self.energy2 = self.energy2, self.energy
-        if self.keps:
-            for name in self.ke:
-                K.gather_rows(self.ke2[name], self.ke[name], self.partindex, n)
-            self.ke, self.ke2 = self.ke2, self.ke
-        if self.grenier:
-            K.gather_rows(self.vol2, self.vol, self.partindex, n)
-            self.vol, self.vol2 = self.vol2, self.vol
-        if self.granular:
-            K.gather_rows(self.effpres2, self.effpres, self.partindex, n)
-            self.effpres, self.effpres2 = self.effpres2, self.effpres
+        for b in self._bufs:         # the arrays that reorderDataAndFindCellStart does not take along
+            if b.resort == GATHER:
+                for dst, src in zip(_tensors(getattr(self, b.name + "2")), _tensors(getattr(self, b.name))):
+                    K.gather_rows(dst, src, self.partindex, n)
+        self._swap(*self._resorted)
         if self.world == 1:
             if self.track_particle_count:
                 before = self.n_local
@@ -359,7 +424,7 @@ class MultiGpuEngine:
         followed by the UPDATE_EXTERNAL of what it wrote"""
         K, n, ni = self.k, self.n_local, self.n_int
         ext = (lambda ts: self._exchange(ts)) if self.world > 1 else (lambda ts: None)
-        be_new = self.boundelements2 if self.sa_moving else self.boundelements      # the elements of the new state
+        be_new = self._state_of(self.pos2).boundelements      # the elements of the new state
         if self.sa_density_sum:
             # DENSITY_SUM [+ CALC_DENSITY_DIFFUSION + APPLY_DENSITY_DIFFUSION] (PredictorCorrectorIntegrator.cc:607-659): density and
             # gamma of the new state from the positions of step n and of the new state; BUFFER_FORCES is their scratch
@@ -380,7 +445,7 @@ class MultiGpuEngine:
                                  self.cellStart, self.neibslist, n, ni)
             ext([self.gradgamma2])
         if self.keps:
-            ke = self.ke2
+            ke = self._state_of(self.pos2).ke
             K.sa_segment_bc_keps(self.vel2, self.gradgamma2, ke, self.pos2, self.vertices, self.boundelements, self.info, self.hash,
                                  self.cellStart, self.neibslist, n, ni, step)
             ext([self.vel2, self.gradgamma2, ke["tke"], ke["eps"], ke["eulervel"]])
@@ -406,7 +471,7 @@ class MultiGpuEngine:
         dt = float(np.float32(np.float32(self.d_dt.item()) * np.float32(0.5 if step == 1 else 1.0)))      # dt_op, on the host
         # with bodies that move as well (the option set of CompleteSaExample.cu:46): the elements of step n and of the new state in
         # the density summation, those of the new state in everything that follows (as without open boundaries, _sa_post_euler)
-        be_new = self.boundelements2 if self.sa_moving else self.boundelements
+        be_new = self._state_of(self.pos2).boundelements
         if self.sa_moving:
             K.sa_density_sum_io_moving(self.vel2, self.gradgamma2, self.forces, self.pos, self.pos2, self.vel, self.eulervel, self.gradgamma,
                                        self.boundelements, be_new, self.vertpos, self.info, self.hash, self.cellStart, self.neibslist,
@@ -500,7 +565,7 @@ class MultiGpuEngine:
             ext([self.boundelements])
             K.sa_init_gamma(self.gradgamma2, self.gradgamma, self.pos, self.boundelements, self.vertpos, self.info, self.hash,
                             self.cellStart, self.neibslist, n, ni)
-            self.gradgamma, self.gradgamma2 = self.gradgamma2, self.gradgamma
+            self._swap("gradgamma")
             ext([self.gradgamma])
         if self.io:
             # with open boundaries (:150-290): corner vertices, the initial masses of the open vertices, the imposed values, then
@@ -513,7 +578,7 @@ class MultiGpuEngine:
             ext([self.forces])      # a vertex divides by the counts of the vertices it shares segments with, the halo's among them
             K.sa_init_io_mass(self.pos2, self.pos, self.forces, self.vertices, self.hash, self.info, self.cellStart, self.neibslist, n, ni)
             self.pos2[ni:n] = self.pos[ni:n]      # (the pass writes the internal rows)
-            self.pos, self.pos2 = self.pos2, self.pos
+            self._swap("pos")
             ext([self.pos])
             self._io_impose(self.pos, self.vel, self.eulervel)
             K.sa_segment_bc_io(self.vel, self.gradgamma, self.eulervel, self.pos, self.vertices, self.boundelements, self.info,
@@ -569,18 +634,7 @@ class MultiGpuEngine:
         self.recv_l = (n_int, n_int + rl)
         self.recv_r = (n_int + rl, n_int + rl + rr)
         self.n_local = n_int + rl + rr
-        state = [self.pos, self.vel, self.info, self.hash]
-        if self.grenier:
-            state.append(self.vol)           # BUFFER_VOLUME is particle state: the halo copies integrate theirs from the exchanged forces
-        if self.energy_on:
-            state.append(self.energy)
-        if self.sa:      # BUFFER_VERTICES / BOUNDELEMENTS / GRADGAMMA are particle state too
-            state += [self.vertices, self.boundelements, self.gradgamma]
-        if self.io:      # ... and BUFFER_EULERVEL (the halo's vertices and segments enter the forces with theirs)
-            state.append(self.eulervel)
-        if self.keps:
-            state += list(self.ke.values())
-        self._exchange(state)
+        self._exchange(self.halo_state())
         # imported cells are OUTER_EDGE cells here whatever they are at home
         if self.n_local > n_int:
             hs = self.hash[n_int:self.n_local]
@@ -621,10 +675,9 @@ class MultiGpuEngine:
                 self._exchange(self.tau)
         # the forces entry of this option set, as a function of the particle range and the offset into the CFL array
         if self.sa:      # forces engine of SA_BOUNDARY: the state's gamma, the boundary elements, the vertex offsets of the segments
-            ggam = self.gradgamma if pos is self.pos else self.gradgamma2
-            be = self.boundelements2 if (self.sa_moving and pos is not self.pos) else self.boundelements
-
-            ke = (self.ke if pos is self.pos else self.ke2) if (self.keps and run_mode == D.SIMULATE) else None
+            st = self._state_of(pos)      # ... its k-epsilon fields, its Eulerian velocities
+            ggam, be = st.gradgamma, st.boundelements
+            ke = st.ke if (self.keps and run_mode == D.SIMULATE) else None
             if ke is not None:
                 K.memset(self.cfl_keps, 0)
             # bodies that feel the fluid (FG_COMPUTE_FORCE segments): the pressure force on their elements rides with the pass
@@ -643,8 +696,7 @@ class MultiGpuEngine:
                                             self.neibslist, ggam, self.boundelements, self.vertpos, ke, self.n_local, frm, to, off,
                                             cfl_gamma=self.cfl_gamma)
                 if self.io:      # the Eulerian velocity of the open boundaries in the viscous terms and in the gamma CFL condition
-                    ev = self.eulervel if pos is self.pos else self.eulervel2
-                    return K.forces_sa_io(self.forces, self.cfl, pos, vel, ev, self.info, self.hash, self.cellStart, self.neibslist, ggam,
+                    return K.forces_sa_io(self.forces, self.cfl, pos, vel, st.eulervel, self.info, self.hash, self.cellStart, self.neibslist, ggam,
                                           be, self.vertpos, self.n_local, frm, to, off, cfl_gamma=self.cfl_gamma)
                 return K.forces_sa(self.forces, self.cfl, pos, vel, self.info, self.hash, self.cellStart, self.neibslist, ggam,
                                    be, self.vertpos, self.n_local, frm, to, off, cfl_gamma=self.cfl_gamma, run_mode=run_mode)
@@ -665,8 +717,7 @@ class MultiGpuEngine:
         elif self.grenier and run_mode == D.SIMULATE:
             # COMPUTE_DENSITY on the state the forces read, UPDATE_EXTERNAL of sigma and of the rewritten velocity buffer
             # (PredictorCorrectorIntegrator.cc:443-458), then the Grenier forces
-            vol = self.vol if pos is self.pos else self.vol2
-            K.compute_density(self.sigma, vel, pos, self.info, self.hash, vol, self.cellStart, self.neibslist, self.n_int)
+            K.compute_density(self.sigma, vel, pos, self.info, self.hash, self._state_of(pos).vol, self.cellStart, self.neibslist, self.n_int)
             if self.world > 1:
                 self._exchange([self.sigma, vel])
 
@@ -749,7 +800,7 @@ class MultiGpuEngine:
                     K.filter(ftype, self.vel2, self.pos, self.vel, self.info, self.hash, self.cellStart, self.neibslist, n, self.n_int)
                     if self.world > 1:
                         self._exchange([self.vel2])
-                    self.vel, self.vel2 = self.vel2, self.vel
+                    self._swap("vel")
         ekw = dict(xsph=self.xsph) if self.xsph is not None else {}
         if self.bodies is not None:
             dt_host = float(self.d_dt.item())       # the callback needs dt on the host: one synchronisation per step
@@ -780,7 +831,6 @@ class MultiGpuEngine:
             m = self.bodies.timestep(2, dt_host, self.t_host); K.set_body_motion(m, self.sp.numforcesbodies > 0)
         if self.grenier:     # the volumes of n* are overwritten by those of n+1, like pos and vel
             K.euler_grenier(self.pos2, self.vel2, self.vol2, self.pos, self.vel, self.vol, self.info, self.hash, self.forces, n, self.d_dt, 1.0, 2)
-            self.vol, self.vol2 = self.vol2, self.vol
         else:
             K.euler(self.pos2, self.vel2, self.pos, self.vel, self.info, self.hash, self.forces, n, self.d_dt, 1.0, 2, **ekw)
             self._rows_for = (self.vel2, self.vel2._version)
@@ -788,30 +838,19 @@ class MultiGpuEngine:
             K.sa_update_normals(self.boundelements2, self.boundelements, self.info, n, n)
         if self.energy_on:
             K.euler_internal_energy(self.energy2, self.energy, self.dedt, self.pos, self.info, n, self.d_dt, 1.0)
-            self.energy, self.energy2 = self.energy2, self.energy
         if self.keps:
             K.euler_keps(self.ke2, self.ke, self.dkde, self.forces, self.pos, self.info, n, self.d_dt, 1.0)
         if self.io:
             self._sa_post_euler_io(2)        # (the particle count has grown by the released particles: n is stale from here on)
-            self.gradgamma, self.gradgamma2 = self.gradgamma2, self.gradgamma
-            self.eulervel, self.eulervel2 = self.eulervel2, self.eulervel
-            if self.sa_moving:
-                self.boundelements, self.boundelements2 = self.boundelements2, self.boundelements
         elif self.sa:
             self._sa_post_euler(2)
-            if self.keps:
-                self.ke, self.ke2 = self.ke2, self.ke
-            self.gradgamma, self.gradgamma2 = self.gradgamma2, self.gradgamma
-            if self.sa_moving:
-                self.boundelements, self.boundelements2 = self.boundelements2, self.boundelements
         if self.granular:            # POSTCORR_EFFPRES on the state n+1
             self._solve_effpres("corrector", self.pos2, self.vel2)
         if self.bodies is not None:                 # EULER_UPLOAD_OBJECTS_CG in the post-corrector phase (:331-332)
             K.set_body_cg_integration(m)
             self._last_motion = m
             self.t_host += dt_host                  # the same double += float as on the device
-        self.pos, self.pos2 = self.pos2, self.pos
-        self.vel, self.vel2 = self.vel2, self.vel
+        self._swap(*self._stepped)      # n+1 becomes n: every buffer the step wrote a new copy of (BUFFERS)
         # TIME_STEP_EPILOGUE: t += dt ; dt = min(dt_pred, dt_corr), over all devices (GPUSPH.cc:650-657)
         K.time_advance(self.d_t, self.d_dt)
         if self.world > 1:
@@ -972,11 +1011,7 @@ class MultiGpuEngine:
 
     def download_internal(self):
         n = self.n_int
-        return {"pos": self.pos[:n].cpu().numpy(), "vel": self.vel[:n].cpu().numpy(),
-                "info": self.info[:n].cpu().numpy().view(np.uint16), "hash": self.hash[:n].cpu().numpy().view(np.uint32),
-                "forces": self.forces[:n].cpu().numpy(),
-                **({"vol": self.vol[:n].cpu().numpy()} if self.grenier else {}),
-                **({"energy": self.energy[:n].cpu().numpy()} if self.energy_on else {}),
-                **({"effpres": self.effpres[:n].cpu().numpy()} if self.granular else {}),
-                **({"gradgamma": self.gradgamma[:n].cpu().numpy(), "boundelements": self.boundelements[:n].cpu().numpy()} if self.sa else {}),
-                **({k: v[:n].cpu().numpy() for k, v in self.ke.items()} if self.keps else {})}
+        out = {k: t[:n].cpu().numpy() for b in self._bufs if b.download for k, t in _items(b.name, getattr(self, b.name))}
+        out.update(info=self.info[:n].cpu().numpy().view(np.uint16), hash=self.hash[:n].cpu().numpy().view(np.uint32),
+                   forces=self.forces[:n].cpu().numpy())
+        return out
