@@ -141,6 +141,8 @@ struct Self {
 #define DIFF_NONE 0
 #define DIFF_COLAGROSSI 1
 #define DIFF_FERRARI 2
+// Colagrossi with a gravity that has a z component only: g.r is the one product g_z r_z (pair_interact_pk; the plain tiled pass only)
+#define DIFF_COLAGROSSI_GZ 3
 
 // TURB template codes: the turbulence model in the low bits, SPHX_TURB_NEWT set for the NEWTONIAN rheology
 #define SPHX_TURB_NEWT 8
@@ -775,8 +777,12 @@ __device__ __forceinline__ void pair_interact_pk(const DevParams &p, const Self 
 	const v2f mf = {fminf(n0.w*f.x, 0.0f), fminf(n1.w*f.y, 0.0f)};
 
 	v2f dsel = {0.0f, 0.0f};
-	if (COLAGROSSI == DIFF_COLAGROSSI) {
-		const v2f gdotr = pk_fma(pk_splat(p.gravity[2]), rz, pk_fma(pk_splat(p.gravity[1]), ry, pk_splat(p.gravity[0])*rx));
+	if (COLAGROSSI == DIFF_COLAGROSSI || COLAGROSSI == DIFF_COLAGROSSI_GZ) {
+		// DIFF_COLAGROSSI_GZ (chosen by the host for g_x = g_y = 0, plain_gravity_z): one packed multiply instead of a multiply
+		// and two FMAs.  Same bits: the two terms left out are exact zeros, fma(g_z, r_z, +-0) rounds as g_z r_z, and where
+		// r_z = 0 only the sign of a zero differs, which fabsf below takes off
+		const v2f gdotr = COLAGROSSI == DIFF_COLAGROSSI_GZ ? pk_splat(p.gravity[2])*rz :
+			pk_fma(pk_splat(p.gravity[2]), rz, pk_fma(pk_splat(p.gravity[1]), ry, pk_splat(p.gravity[0])*rx));
 		const v2f gr = gdotr*pk_splat(s.rho);
 		const bool d0 = rt_diffuse && !(fabsf(s.P - a0.z) < fabsf(gr.x)), d1 = rt_diffuse && !(fabsf(s.P - a1.z) < fabsf(gr.y));
 		const v2f ratio = {fmaf(a0.w, s.inv_rho, -1.0f), fmaf(a1.w, s.inv_rho, -1.0f)};
@@ -1949,6 +1955,17 @@ static void launch_tile(const sphx_ctx *ctx, hipStream_t stream, const ForcesArg
 			ctx->tiles, ctx->tile_ctl, ctx->cell_end_copy);
 }
 
+// The plain pass (pair_interact_pk with the Colagrossi term) has a second instantiation for a gravity along z, which is what
+// nearly every problem has: is this launch one of its?  The values are the context's own, so a gravity that changes during
+// a run is looked at again at every launch; -0.0f counts as zero.  sphx_dbg_forces_general_gravity turns it off for a context.
+static bool plain_gravity_z(const sphx_ctx *ctx)
+{
+	const DevParams &p = ctx->dev;
+	return !ctx->general_gravity && p.gravity[0] == 0.0f && p.gravity[1] == 0.0f &&
+		p.kerneltype == SPHX_WENDLAND && p.turbmodel == SPHX_ARTIFICIAL && p.numfluids <= 1 && p.densitydiff == SPHX_COLAGROSSI &&
+		p.boundarytype != SPHX_LJ_BOUNDARY;
+}
+
 // launches the tiled kernel when the tiling of this neighbour list is available, plus the generic
 // kernel guarded by the device-side overflow flag (it returns at once when the tiles were used)
 template<int KERNEL>
@@ -1978,7 +1995,16 @@ static int launch_forces_k(const sphx_ctx *ctx, dim3 grid, hipStream_t stream, c
 		else launch_forces_mf<KERNEL, T, DIFF_NONE>(mf, grid, stream, p, a, G); } while (0)
 	switch (p.turbmodel) {
 	case SPHX_ARTIFICIAL:
-		SPHX_LAUNCH_TILE(SPHX_ARTIFICIAL);
+		if constexpr (KERNEL == SPHX_WENDLAND) {      // (this part alone holds the second instantiation)
+			if (use_tiles && plain_gravity_z(ctx)) {
+				ForcesTimer tt(ctx, stream, true);
+				forces_tile_kernel<SPHX_WENDLAND, SPHX_ARTIFICIAL, DIFF_COLAGROSSI_GZ, false><<<ctx->tile_grid, TILE_THREADS, 0, stream>>>(ctx->dev, a,
+					ctx->tiles, ctx->tile_ctl, ctx->cell_end_copy);
+			} else
+				SPHX_LAUNCH_TILE(SPHX_ARTIFICIAL);
+		} else {
+			SPHX_LAUNCH_TILE(SPHX_ARTIFICIAL);
+		}
 		SPHX_LAUNCH_GENERIC(SPHX_ARTIFICIAL, guard);
 		break;
 	case SPHX_SPS:
@@ -2028,11 +2054,16 @@ void sphx_part_sa_tile(const sphx_ctx *ctx, hipStream_t stream, const ForcesArgs
 #undef SPHX_SA_TILE_D
 }
 #elif defined(SPHX_FORCES_PART) && defined(SPHX_PROBE_PLAIN)
-// one instantiation alone, for reading its ISA (scripts/probe_plain_isa.sh): the plain forces pass of the bench workload
+// two instantiations alone, for reading their ISA (scripts/probe_plain_isa.sh): the plain forces pass of the bench workload
+// (gravity along z) and its form for any gravity
 void sphx_probe_plain(const sphx_ctx *ctx, hipStream_t stream, const ForcesArgs &a)
 {
-	forces_tile_kernel<SPHX_WENDLAND, SPHX_ARTIFICIAL, DIFF_COLAGROSSI, false><<<ctx->tile_grid, TILE_THREADS, 0, stream>>>(ctx->dev, a,
-		ctx->tiles, ctx->tile_ctl, ctx->cell_end_copy);
+	if (plain_gravity_z(ctx))
+		forces_tile_kernel<SPHX_WENDLAND, SPHX_ARTIFICIAL, DIFF_COLAGROSSI_GZ, false><<<ctx->tile_grid, TILE_THREADS, 0, stream>>>(ctx->dev, a,
+			ctx->tiles, ctx->tile_ctl, ctx->cell_end_copy);
+	else
+		forces_tile_kernel<SPHX_WENDLAND, SPHX_ARTIFICIAL, DIFF_COLAGROSSI, false><<<ctx->tile_grid, TILE_THREADS, 0, stream>>>(ctx->dev, a,
+			ctx->tiles, ctx->tile_ctl, ctx->cell_end_copy);
 }
 #elif defined(SPHX_FORCES_PART)
 #define SPHX_PASTE2(a, b) a##b
@@ -2836,6 +2867,16 @@ extern "C" int sphx_dbg_tiles_usable(sphx_ctx *ctx)
 	uint32_t ctl[2];
 	if (hipMemcpy(ctl, ctx->tile_ctl, sizeof(ctl), hipMemcpyDeviceToHost) != hipSuccess) return -1;
 	return (ctl[0] > 0u && ctl[1] == 0u) ? 1 : 0;
+}
+
+// tests only, not part of include/sphx.h: on != 0 keeps the plain tiled pass of this context on the instantiation for any gravity
+// (plain_gravity_z), so that a test can hold the one for a gravity along z against it bit for bit; on < 0 changes nothing.
+// -> 1 when a tiled plain pass of this context now takes the instantiation for a gravity along z, 0 when it does not
+extern "C" int sphx_dbg_forces_general_gravity(sphx_ctx *ctx, int on)
+{
+	if (!ctx) return -1;
+	if (on >= 0) ctx->general_gravity = on != 0;
+	return plain_gravity_z(ctx) ? 1 : 0;
 }
 
 // Optional profiling hook (bench.py): when enabled, every forces pass records a pair of HIP events on its launch

@@ -4,6 +4,7 @@
 #include "sphx_internal.h"
 #include <cstring>
 #include <cstdlib>
+#include <type_traits>
 
 #define BLOCK_NEIBS   256
 // (tests/hostemu compiles this file for the host and runs the kernel's waves as fibres: its stand-in header defines the macro)
@@ -155,7 +156,8 @@ struct SaNeibArgs {
 // The distance tests of the list build on the matrix cores (round 6).
 //
 // The walk below ("general walk") tests ~475 candidates per particle at ~17 vector instructions each, one lane per home
-// particle: 7.7 G vector instructions per build at 32 M particles, 13 ms.  The test itself -- |x_i - x_j|^2 < R^2 for every
+// particle: 7.7 G vector instructions per build at 32 M particles, 13 ms (as measured then; with the self test confined to the
+// home cell, fluid_segment below, ~15.25 per candidate in 26 of the 27 cells, 7.0 G and 12.6 ms).  The test itself -- |x_i - x_j|^2 < R^2 for every
 // home particle of a wave against every particle of the cells around them -- is a dense contraction: with the wave's 64 home
 // particles as columns and 32 candidates as rows, |c|^2 - 2 c.h + (|h|^2 - R^2) is a 32 x 64 product of inner dimension 4, two
 // v_mfma_f32_32x32x2_f32 per half of the wave, and what is left to the vector unit per pair is ONE instruction that shifts the
@@ -618,7 +620,11 @@ build_neibs_kernel(DevParams p, SaNeibArgs sa, neibdata *__restrict__ neibsList,
 			uint32_t encv = code;             // cell code still owed to the first entry stored for this (cell, type) run
 			uint32_t neib_type = PT_FLUID;
 			// --- fluid segment: type known, NEIB_MLP position gathers in flight ---
-			const uint32_t selfrel = (cell == 13u) ? index - bucketStart : 0xFFFFFFFFu;
+			// SELF: the segment is the home cell's (c = 13), the only one that holds the particle itself.  The cell number is
+			// wave-uniform, so the two copies of the scan are chosen by a scalar branch per cell and the other 26 cells carry no
+			// self test at all
+			auto fluid_segment = [&](auto selfTag) {
+			constexpr bool SELF = decltype(selfTag)::value;
 			for (uint32_t j0 = bucketStart; __builtin_amdgcn_ballot_w64(j0 < fluidEnd); j0 += NEIB_MLP) {
 				// the loop is kept wave-uniform (a lane past its segment masks its candidates) so that the ring can be
 				// flushed by the whole wave from inside it
@@ -647,13 +653,14 @@ build_neibs_kernel(DevParams p, SaNeibArgs sa, neibdata *__restrict__ neibsList,
 				}
 				const uint32_t jrel = j0 - bucketStart;
 				const uint32_t rem = in ? fluidEnd - j0 : 0u;
+				// which candidate of this batch is the particle itself (a number below NEIB_MLP in one batch of the home cell, in
+				// no other): one subtraction per batch, and the test of a candidate is a compare with the literal u
+				const uint32_t selfu = index - j0;
 				if (!__builtin_amdgcn_ballot_w64(nf + (uint32_t)NEIB_MLP >= p.neibboundpos)) {
 #pragma unroll
 					for (int u = 0; u < NEIB_MLP; ++u) {
 						const float r2a = fmaf(0.0f, cp[u].w, r2[u]);
-						// (selfrel is no index of any other cell, so the self test needs no "is this the home cell" around it: as a
-						// select between two per-lane flags that guard cost five vector instructions per candidate)
-						const bool acc = (r2a < sqinfluenceradius) && ((uint32_t)u < rem) && (jrel + (uint32_t)u != selfrel);
+						const bool acc = (r2a < sqinfluenceradius) && ((uint32_t)u < rem) && (!SELF || selfu != (uint32_t)u);
 						ring.fring[nf % (uint32_t)NEIB_FRING][lane] = (neibdata)(jrel + (uint32_t)u + encv);
 						encv = acc ? 0u : encv;
 						nf += acc ? 1u : 0u;
@@ -664,7 +671,7 @@ build_neibs_kernel(DevParams p, SaNeibArgs sa, neibdata *__restrict__ neibsList,
 #pragma unroll
 				for (int u = 0; u < NEIB_MLP; ++u) {
 					// (the candidate's index j0 + u is named nowhere: its row offset is an immediate of the load above)
-					const bool acc = (r2[u] < sqinfluenceradius) && ((uint32_t)u < rem) && (jrel + (uint32_t)u != selfrel) &&
+					const bool acc = (r2[u] < sqinfluenceradius) && ((uint32_t)u < rem) && (!SELF || selfu != (uint32_t)u) &&
 						is_active_w(cp[u].w);
 					nf += acc ? 1u : 0u;
 					const bool ok = acc && !too_many_neibs(p, nf, nb, nv, PT_FLUID);
@@ -673,6 +680,8 @@ build_neibs_kernel(DevParams p, SaNeibArgs sa, neibdata *__restrict__ neibsList,
 					encv = ok ? 0u : encv;
 				}
 			}
+			};
+			if (cell == 13u) fluid_segment(std::true_type()); else fluid_segment(std::false_type());
 			ring.room_b(NEIB_BRING/2, 0);
 			// --- non-fluid tail (boundary / vertex / testpoint candidates): the reference's loop as is ---
 			for (uint32_t neib_index = max(fluidEnd, bucketStart); neib_index < bucketEnd; ++neib_index) {

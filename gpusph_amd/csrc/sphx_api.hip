@@ -56,6 +56,7 @@ extern "C" int sphx_create(sphx_ctx **out, int device)
 	ctx->disable_tiles = is1("SPHX_DISABLE_TILES");
 	ctx->neibs_mfma = is1("SPHX_NEIBS_MFMA");
 	ctx->tiling_inline = getenv("SPHX_TILING_INLINE") != nullptr;
+	ctx->general_gravity = false;
 	ctx->tile_debug = 0;
 #ifdef SPHX_TILE_DEBUG_BUILD
 	const char *dbg = getenv("SPHX_TILE_DEBUG");

@@ -220,6 +220,7 @@ struct sphx_ctx {
 	bool        disable_tiles; // SPHX_DISABLE_TILES=1 in the environment (A/B testing)
 	bool        tiling_inline; // SPHX_TILING_INLINE set in the environment when the context was created: no side stream
 	bool        neibs_mfma;    // SPHX_NEIBS_MFMA=1 in the environment when the context was created: the list build's prepass on the matrix cores (neibs_build.hip)
+	bool        general_gravity;  // sphx_dbg_forces_general_gravity (tests): the plain pass never takes its vertical-gravity instantiation
 	int         tile_debug;    // SPHX_TILE_DEBUG (timing experiments; only with -DSPHX_TILE_DEBUG_BUILD)
 	unsigned long long *tile_prof;   // ... & 16: phase timers of the tiled forces kernel
 	bool        time_forces;   // sphx_forces_timing: bracket the dominant forces kernel with HIP events
