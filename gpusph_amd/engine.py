@@ -73,25 +73,6 @@ class TimestepEngine(MultiGpuEngine):
                                  % (info.hasTooManyNeibs, info.hasMaxNeibs[0], info.hasMaxNeibs[1]))
         return info
 
-    def _forces(self, pos, vel, step, combine_min, run_mode=D.SIMULATE):
-        """one forces pass (CALC_VISC, FORCES, dtreduce) on the given state"""
-        self._forces_pass(pos, vel, combine_min, run_mode=run_mode, step=step)
-
-    def _euler(self, step, dt_scale, run_mode=D.SIMULATE):
-        kw = dict(xsph=self.xsph) if self.xsph is not None else {}
-        if run_mode != D.SIMULATE:
-            kw["run_mode"] = run_mode
-        self.k.euler(self.pos2, self.vel2, self.pos, self.vel, self.info, self.hash, self.forces, self.n_local, self.d_dt,
-                     dt_scale, step, **kw)
-
-    def apply_filter(self, filtertype):
-        """FILTER_CALL phase (src/integrators/PredictorCorrectorIntegrator.cc:831-859): read the unfiltered
-        velocities, write the filtered ones, swap the two VEL buffers."""
-        self._rows_for = None      # the velocity buffer may be rewritten behind torch's back (multigpu.py, _rows_for)
-        n = self.n_local
-        self.k.filter(int(filtertype), self.vel2, self.pos, self.vel, self.info, self.hash, self.cellStart, self.neibslist, n, n)
-        self._swap("vel")
-
     # ------------------------------------------------------------------ post-processing (before writes)
     def postprocess(self, pptype, normals=False):
         """POSTPROCESS command (src/GPUWorker.cc runCommand<POSTPROCESS>): VORTICITY returns a [n,3] tensor,
@@ -114,11 +95,10 @@ class TimestepEngine(MultiGpuEngine):
         if detect and normals:
             nrm = out = torch.empty((self.alloc, 4), dtype=torch.float32, device=self.device)
         if pptype == D.TESTPOINTS and self.keps:      # BUFFER_TKE / BUFFER_EPSILON of the test points are written with the velocity
-            self.k.postprocess_testpoints_keps(self.vel, self.ke["tke"], self.ke["eps"], self.pos, self.info, self.hash, self.cellStart,
-                                               self.neibslist, n)
+            self.k.postprocess_testpoints_keps(self.vel, self.ke["tke"], self.ke["eps"], self.pos, *self._lists, n)
             return None
         self.k.postprocess(pptype, vort, self.vel if pptype == D.TESTPOINTS else None, self.info if detect else None, nrm,
-                           self.pos, self.vel, self.info, self.hash, self.cellStart, self.neibslist, n,
+                           self.pos, self.vel, *self._lists, n,
                            getattr(pp, "cosconeanglefluid", 0.86), getattr(pp, "cosconeanglenonfluid", 0.5))
         if detect:
             self._surface_for = self._state_key()
@@ -136,13 +116,10 @@ class TimestepEngine(MultiGpuEngine):
         self._forces(self.pos, self.vel, 1, 0, D.REPACK)
         self._euler(1, 1.0, D.REPACK)
         if self.sa:      # INTEGRATE_GAMMA of the new state (RepackingIntegrator.cc:386-405); gamma by quadrature only
-            self.k.sa_integrate_gamma(self.gradgamma2, self.gradgamma, self.pos2, self.boundelements, self.vertpos, self.info, self.hash,
-                                      self.cellStart, self.neibslist, self.n_local, self.n_local)
+            self.k.sa_integrate_gamma(self.gradgamma2, self.gradgamma, self.pos2, self.boundelements, self.vertpos, *self._lists,
+                                      self.n_local, self.n_local)
         # what a repacking iteration wrote a new copy of: no other state buffer moves (BUFFERS in multigpu.py)
-        self._swap(*(("pos", "vel", "gradgamma") if self.sa else ("pos", "vel")))
-        self.k.time_advance(self.d_t, self.d_dt)
-        self.d_dt, self.d_dt_next = self.d_dt_next, self.d_dt
-        self.iterations += 1
+        self._finish_step(("pos", "vel", "gradgamma") if self.sa else ("pos", "vel"))
 
     def repack(self, maxiter=None, reset=True):
         """`GPUSPH --repack`: run the repacking integrator for repack_maxiter iterations (GPUSPH.cc:196-201,

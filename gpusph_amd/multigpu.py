@@ -345,6 +345,12 @@ class MultiGpuEngine:
     def _init_volume(self, arrs, mask, n0):
         self.k.init_volume(self.vol, self.pos, self.vel, self.info, n0)      # GPUSPH.cc:495-496
 
+    @property
+    def _lists(self):
+        """what nearly every pass over the neighbours reads beside the state, to splat into the call; read when the call is made (a
+        re-sort renames info and hash)"""
+        return self.info, self.hash, self.cellStart, self.neibslist
+
     def _swap(self, *names):
         """rename <name> <-> <name>2"""
         for name in names:
@@ -375,7 +381,10 @@ class MultiGpuEngine:
         return left, right
 
     def _exchange(self, tensors):
-        """send my edge layers / receive the halo layers of every tensor in `tensors` (dim-0 ranges)"""
+        """UPDATE_EXTERNAL of what a pass over the internal particles wrote: send my edge layers / receive the halo layers of
+        every tensor in `tensors` (dim-0 ranges).  A single domain has no halo and no transport."""
+        if self.transport is None:
+            return
         left, right = self._neighbours()
         self.halo_bytes += self.transport.exchange(tensors, left, right, self.send_l, self.recv_l, self.send_r, self.recv_r)
 
@@ -413,89 +422,95 @@ class MultiGpuEngine:
         if self.sa:
             K.build_neibs_sa(self.neibslist, self.vertpos, self.pos, self.info, self.vertices, self.boundelements, self.hash,
                              self.cellStart, self.cellEnd, self.n_local, self.n_int)
-            if self.world > 1:       # the vertex offsets of the halo segments (UPDATE_EXTERNAL of BUFFER_VERTPOS after BUILDNEIBS)
-                self._exchange(self.vertpos)
+            self._exchange(self.vertpos)      # the vertex offsets of the halo segments (UPDATE_EXTERNAL of BUFFER_VERTPOS after BUILDNEIBS)
         else:
             K.build_neibs(self.neibslist, self.pos, self.info, self.hash, self.cellStart, self.cellEnd, self.n_local, self.n_int)
+
+    def _dt_op(self, step):
+        """dt of the substep on the host, as the reference's commands carry it: half a step and a whole step are exact in float"""
+        return float(np.float32(self.d_dt.item()) * np.float32(0.5 if step == 1 else 1.0))
+
+    def _sa_bc(self, st, step, run_mode=D.SIMULATE):
+        """SA_CALC_SEGMENT_BOUNDARY_CONDITIONS and SA_CALC_VERTEX_BOUNDARY_CONDITIONS on the state `st` (_state_of), in place, each
+        over the internal particles and followed by the UPDATE_EXTERNAL of what it wrote; with k-epsilon the passes that also set
+        k, epsilon and the Eulerian velocity of the wall"""
+        K, n, ni = self.k, self.n_local, self.n_int
+        if self.keps and run_mode == D.SIMULATE:
+            ke = st.ke
+            walls = [ke["tke"], ke["eps"], ke["eulervel"]]
+            K.sa_segment_bc_keps(st.vel, st.gradgamma, ke, st.pos, self.vertices, self.boundelements, *self._lists, n, ni, step)
+            self._exchange([st.vel, st.gradgamma] + walls)
+            K.sa_vertex_bc_keps(st.vel, st.gradgamma, ke, self.vertices, self.boundelements, st.pos, *self._lists, n, ni, step)
+            self._exchange([st.vel] + walls)
+            return
+        K.sa_segment_bc(st.vel, st.gradgamma, st.pos, self.vertices, st.boundelements, *self._lists, n, ni, step, run_mode)
+        self._exchange([st.vel, st.gradgamma])
+        K.sa_vertex_bc(st.vel, st.gradgamma, st.pos, *self._lists, n, ni, step, run_mode)
+        self._exchange([st.vel])
+
+    def _sa_bc_io(self, st, dt, step):
+        """The same pair with open boundaries, on the state `st`: IMPOSE_OPEN_BOUNDARY_CONDITION (the problem's values; it consumes
+        and clears the water depth, the maximum over the devices), the segment conditions, in the last step FIND_OUTGOING_SEGMENT,
+        the vertex conditions (vertex masses; in the last step the take-over of outgoing particles and the release of new ones: the
+        particle count grows), in the last step DISABLE_OUTGOING_PARTS"""
+        K, n, ni = self.k, self.n_local, self.n_int
+        self._io_impose(st.pos, st.vel, st.eulervel)
+        K.sa_segment_bc_io(st.vel, st.gradgamma, st.eulervel, st.pos, self.vertices, st.boundelements, *self._lists, n, ni, step)
+        self._exchange([st.vel, st.gradgamma, st.eulervel])
+        if step == 2:
+            K.sa_find_outgoing_segment(st.pos, st.vel, self.vertices, st.gradgamma, self.vertpos, st.boundelements, *self._lists, n, ni)
+            self._exchange([self.vertices, st.gradgamma])      # the marks: a vertex takes over from the halo's particles too
+        self._io_vertex_bc(st.pos, st.vel, st.gradgamma, st.eulervel, dt, step, st.boundelements)
+        if step == 2:
+            K.sa_disable_outgoing_parts(st.pos, self.vertices, self.info, self.n_local)
 
     def _sa_post_euler(self, step):
         """INTEGRATE_GAMMA on the new positions (always from the gamma of step n), then the boundary conditions of the new
         state (PredictorCorrectorIntegrator.cc:661-684 and the post-step phases); every pass covers the internal particles and is
         followed by the UPDATE_EXTERNAL of what it wrote"""
         K, n, ni = self.k, self.n_local, self.n_int
-        ext = (lambda ts: self._exchange(ts)) if self.world > 1 else (lambda ts: None)
-        be_new = self._state_of(self.pos2).boundelements      # the elements of the new state
+        new = self._state_of(self.pos2)      # (its elements are those of the new state)
         if self.sa_density_sum:
             # DENSITY_SUM [+ CALC_DENSITY_DIFFUSION + APPLY_DENSITY_DIFFUSION] (PredictorCorrectorIntegrator.cc:607-659): density and
             # gamma of the new state from the positions of step n and of the new state; BUFFER_FORCES is their scratch
             if self.sa_moving:       # ... and from the elements where they were and where they are; gamma of the vertices too
                 K.sa_density_sum_moving(self.vel2, self.gradgamma2, self.forces, self.pos, self.pos2, self.vel, self.gradgamma,
-                                        self.boundelements, be_new, self.vertpos, self.info, self.hash, self.cellStart, self.neibslist, n, ni)
+                                        self.boundelements, new.boundelements, self.vertpos, *self._lists, n, ni)
             else:
                 K.sa_density_sum(self.vel2, self.gradgamma2, self.forces, self.pos, self.pos2, self.vel, self.gradgamma, self.boundelements,
-                                 self.vertpos, self.info, self.hash, self.cellStart, self.neibslist, n, ni)
-            ext([self.vel2, self.gradgamma2])
+                                 self.vertpos, *self._lists, n, ni)
+            self._exchange([self.vel2, self.gradgamma2])
             if self.sp.densitydiffusiontype == D.BREZZI:
-                dt = float(self.d_dt.item()) * (0.5 if step == 1 else 1.0)     # dt_op on the host, as the reference's command has it
-                K.sa_density_diffusion(self.forces, self.pos2, self.vel2, self.gradgamma2, self.info, self.hash, self.cellStart,
-                                       self.neibslist, n, ni, float(np.float32(dt)))
-                ext([self.vel2])
+                K.sa_density_diffusion(self.forces, self.pos2, self.vel2, self.gradgamma2, *self._lists, n, ni, self._dt_op(step))
+                self._exchange([self.vel2])
         else:
-            K.sa_integrate_gamma(self.gradgamma2, self.gradgamma, self.pos2, be_new, self.vertpos, self.info, self.hash,
-                                 self.cellStart, self.neibslist, n, ni)
-            ext([self.gradgamma2])
-        if self.keps:
-            ke = self._state_of(self.pos2).ke
-            K.sa_segment_bc_keps(self.vel2, self.gradgamma2, ke, self.pos2, self.vertices, self.boundelements, self.info, self.hash,
-                                 self.cellStart, self.neibslist, n, ni, step)
-            ext([self.vel2, self.gradgamma2, ke["tke"], ke["eps"], ke["eulervel"]])
-            K.sa_vertex_bc_keps(self.vel2, self.gradgamma2, ke, self.vertices, self.boundelements, self.pos2, self.info, self.hash,
-                                self.cellStart, self.neibslist, n, ni, step)
-            ext([self.vel2, ke["tke"], ke["eps"], ke["eulervel"]])
-            return
-        K.sa_segment_bc(self.vel2, self.gradgamma2, self.pos2, self.vertices, be_new, self.info, self.hash, self.cellStart,
-                        self.neibslist, n, ni, step, D.SIMULATE)
-        ext([self.vel2, self.gradgamma2])
-        K.sa_vertex_bc(self.vel2, self.gradgamma2, self.pos2, self.info, self.hash, self.cellStart, self.neibslist, n, ni, step, D.SIMULATE)
-        ext([self.vel2])
+            K.sa_integrate_gamma(self.gradgamma2, self.gradgamma, self.pos2, new.boundelements, self.vertpos, *self._lists, n, ni)
+            self._exchange([self.gradgamma2])
+        self._sa_bc(new, step)
 
     def _sa_post_euler_io(self, step):
         """The post-Euler commands of a step with ENABLE_INLET_OUTLET (src/integrators/PredictorCorrectorIntegrator.cc:127-300,
-        607-684): DENSITY_SUM [+ density diffusion] with the open boundaries' terms from the state of step n,
-        IMPOSE_OPEN_BOUNDARY_CONDITION (the problem's values; it consumes and clears the water depth, the maximum over the devices),
-        the segment conditions, in the last step FIND_OUTGOING_SEGMENT, the vertex conditions (vertex masses; in the last step
-        the take-over of outgoing particles and the release of new ones: the particle count grows), in the last step
-        DISABLE_OUTGOING_PARTS.  Every pass covers the internal particles and is followed by the UPDATE_EXTERNAL of what it wrote."""
+        607-684): DENSITY_SUM [+ density diffusion] with the open boundaries' terms from the state of step n, then the boundary
+        conditions of the new state (_sa_bc_io).  Every pass covers the internal particles and is followed by the UPDATE_EXTERNAL
+        of what it wrote."""
         K, n, ni = self.k, self.n_local, self.n_int
-        ext = (lambda ts: self._exchange(ts)) if self.world > 1 else (lambda ts: None)
-        dt = float(np.float32(np.float32(self.d_dt.item()) * np.float32(0.5 if step == 1 else 1.0)))      # dt_op, on the host
+        dt = self._dt_op(step)
         # with bodies that move as well (the option set of CompleteSaExample.cu:46): the elements of step n and of the new state in
         # the density summation, those of the new state in everything that follows (as without open boundaries, _sa_post_euler)
-        be_new = self._state_of(self.pos2).boundelements
+        new = self._state_of(self.pos2)
         if self.sa_moving:
             K.sa_density_sum_io_moving(self.vel2, self.gradgamma2, self.forces, self.pos, self.pos2, self.vel, self.eulervel, self.gradgamma,
-                                       self.boundelements, be_new, self.vertpos, self.info, self.hash, self.cellStart, self.neibslist,
-                                       n, ni, dt)
+                                       self.boundelements, new.boundelements, self.vertpos, *self._lists, n, ni, dt)
         else:
             K.sa_density_sum_io(self.vel2, self.gradgamma2, self.forces, self.pos, self.pos2, self.vel, self.eulervel, self.gradgamma,
-                                self.boundelements, self.vertpos, self.info, self.hash, self.cellStart, self.neibslist, n, ni, dt)
-        ext([self.vel2, self.gradgamma2])
+                                self.boundelements, self.vertpos, *self._lists, n, ni, dt)
+        self._exchange([self.vel2, self.gradgamma2])
         if self.sp.densitydiffusiontype == D.BREZZI:
-            K.sa_density_diffusion_io(self.forces, self.pos2, self.vel2, self.gradgamma2, be_new, self.vertpos, self.info,
-                                      self.hash, self.cellStart, self.neibslist, n, ni, dt)
-            ext([self.vel2])
+            K.sa_density_diffusion_io(self.forces, self.pos2, self.vel2, self.gradgamma2, new.boundelements, self.vertpos, *self._lists,
+                                      n, ni, dt)
+            self._exchange([self.vel2])
         self.eulervel2[:n] = self.eulervel[:n]
-        self._io_impose(self.pos2, self.vel2, self.eulervel2)
-        K.sa_segment_bc_io(self.vel2, self.gradgamma2, self.eulervel2, self.pos2, self.vertices, be_new, self.info,
-                           self.hash, self.cellStart, self.neibslist, n, ni, step)
-        ext([self.vel2, self.gradgamma2, self.eulervel2])
-        if step == 2:
-            K.sa_find_outgoing_segment(self.pos2, self.vel2, self.vertices, self.gradgamma2, self.vertpos, be_new,
-                                       self.info, self.hash, self.cellStart, self.neibslist, n, ni)
-            ext([self.vertices, self.gradgamma2])      # the marks: a vertex takes over from the halo's particles too
-        self._io_vertex_bc(self.pos2, self.vel2, self.gradgamma2, self.eulervel2, dt, step, be_new)
-        if step == 2:
-            K.sa_disable_outgoing_parts(self.pos2, self.vertices, self.info, self.n_local)
+        self._sa_bc_io(new, dt, step)
 
     def _io_impose(self, pos, vel, eulervel):
         """IMPOSE_OPEN_BOUNDARY_CONDITION on every particle this device holds (the values are a function of position, time and
@@ -509,22 +524,20 @@ class MultiGpuEngine:
                                     torch.from_numpy(np.array(best, dtype=np.uint32).view(np.int32)).to(self.device))
         self.problem.impose_open_boundaries(pos, vel, eulervel, self.info, self.hash, self.iowaterdepth, self.time(), self.n_local)
 
-    def _io_vertex_bc(self, pos, vel, ggam, eulervel, dt, step, boundelements=None):
+    def _io_vertex_bc(self, pos, vel, ggam, eulervel, dt, step, boundelements):
         """SA_CALC_VERTEX_BOUNDARY_CONDITIONS with open boundaries: the pass writes the vertex masses (and the rows of released
         particles) into `pos`, in place as the reference has it; the new particle count comes back in a device word.  Released
         particles are appended behind everything this device holds (its halo included); they belong to it (the hash of the vertex
         that released them) and are sorted in at the next rebuild"""
         K, n, ni = self.k, self.n_local, self.n_int
         self.io_count[0] = n
-        be = self.boundelements if boundelements is None else boundelements      # (the rows of released particles are written there)
-        K.sa_vertex_bc_io(vel, pos, pos, ggam, eulervel, self.forces, self.vertices, be, self.vertpos,
+        K.sa_vertex_bc_io(vel, pos, pos, ggam, eulervel, self.forces, self.vertices, boundelements, self.vertpos,
                           self.info, self.hash, self.next_ids, self.io_count, self.cellStart, self.neibslist, n, ni, self.alloc,
-                          dt, step, self.num_open_vertices)
+                          dt, step, self.num_open_vertices)      # (the rows of released particles are written to `boundelements` too)
         n2 = int(self.io_count.item()) & 0xFFFFFFFF
         if n2 > self.alloc:
             raise RuntimeError("open boundaries released more particles than the allocation holds (%d > %d)" % (n2, self.alloc))
-        if self.world > 1:
-            self._exchange([pos, vel, eulervel])      # vertex masses, densities and Eulerian velocities of the halo's vertices
+        self._exchange([pos, vel, eulervel])      # vertex masses, densities and Eulerian velocities of the halo's vertices
         self.io_created += n2 - n
         self.n_local = n2
         if self.world == 1:
@@ -553,53 +566,34 @@ class MultiGpuEngine:
         return flux[:nob]
 
     def sa_boundary_conditions(self, step, run_mode=D.SIMULATE):
-        """initializeBoundaryConditionsSequence<SA_BOUNDARY> (src/integrators/PredictorCorrectorIntegrator.cc:117-290) without
-        open boundaries: at initialisation (step 0) the vertex normals and gamma, then in every step the segment and the vertex
-        boundary conditions, in place on the current state; internal particles, then UPDATE_EXTERNAL."""
+        """initializeBoundaryConditionsSequence<SA_BOUNDARY> (src/integrators/PredictorCorrectorIntegrator.cc:117-290): at
+        initialisation (step 0) the vertex normals and gamma, then in every step the segment and the vertex boundary conditions,
+        in place on the current state (_sa_bc; with open boundaries the initialisation sequence only, _sa_bc_io); internal
+        particles, then UPDATE_EXTERNAL."""
         if not self.sa:
             raise ValueError("boundary conditions sequence of a problem without SA_BOUNDARY")
         K, n, ni = self.k, self.n_local, self.n_int
-        ext = (lambda ts: self._exchange(ts)) if self.world > 1 else (lambda ts: None)
         if step == 0:
-            K.sa_compute_vertex_normal(self.boundelements, self.vertices, self.info, self.hash, self.cellStart, self.neibslist, n, ni)
-            ext([self.boundelements])
-            K.sa_init_gamma(self.gradgamma2, self.gradgamma, self.pos, self.boundelements, self.vertpos, self.info, self.hash,
-                            self.cellStart, self.neibslist, n, ni)
+            K.sa_compute_vertex_normal(self.boundelements, self.vertices, *self._lists, n, ni)
+            self._exchange([self.boundelements])
+            K.sa_init_gamma(self.gradgamma2, self.gradgamma, self.pos, self.boundelements, self.vertpos, *self._lists, n, ni)
             self._swap("gradgamma")
-            ext([self.gradgamma])
-        if self.io:
-            # with open boundaries (:150-290): corner vertices, the initial masses of the open vertices, the imposed values, then
-            # the two condition passes of step 0
-            if step != 0 or run_mode != D.SIMULATE:
-                raise NotImplementedError("open boundaries: only the initialisation sequence goes through sa_boundary_conditions")
-            K.sa_identify_corner_vertices(self.pos, self.info, self.hash, self.vertices, self.cellStart, self.neibslist, n, ni)
-            ext([self.info])
-            K.sa_init_io_mass_vertex_count(self.forces, self.pos, self.vertices, self.hash, self.info, self.cellStart, self.neibslist, n, ni)
-            ext([self.forces])      # a vertex divides by the counts of the vertices it shares segments with, the halo's among them
-            K.sa_init_io_mass(self.pos2, self.pos, self.forces, self.vertices, self.hash, self.info, self.cellStart, self.neibslist, n, ni)
-            self.pos2[ni:n] = self.pos[ni:n]      # (the pass writes the internal rows)
-            self._swap("pos")
-            ext([self.pos])
-            self._io_impose(self.pos, self.vel, self.eulervel)
-            K.sa_segment_bc_io(self.vel, self.gradgamma, self.eulervel, self.pos, self.vertices, self.boundelements, self.info,
-                               self.hash, self.cellStart, self.neibslist, n, ni, 0)
-            ext([self.vel, self.gradgamma, self.eulervel])
-            self._io_vertex_bc(self.pos, self.vel, self.gradgamma, self.eulervel, 0.0, 0)
-            return
-        if self.keps and run_mode == D.SIMULATE:
-            ke = self.ke
-            K.sa_segment_bc_keps(self.vel, self.gradgamma, ke, self.pos, self.vertices, self.boundelements, self.info, self.hash,
-                                 self.cellStart, self.neibslist, n, ni, step)
-            ext([self.vel, self.gradgamma, ke["tke"], ke["eps"], ke["eulervel"]])
-            K.sa_vertex_bc_keps(self.vel, self.gradgamma, ke, self.vertices, self.boundelements, self.pos, self.info, self.hash,
-                                self.cellStart, self.neibslist, n, ni, step)
-            ext([self.vel, ke["tke"], ke["eps"], ke["eulervel"]])
-            return
-        K.sa_segment_bc(self.vel, self.gradgamma, self.pos, self.vertices, self.boundelements, self.info, self.hash, self.cellStart,
-                        self.neibslist, n, ni, step, run_mode)
-        ext([self.vel, self.gradgamma])
-        K.sa_vertex_bc(self.vel, self.gradgamma, self.pos, self.info, self.hash, self.cellStart, self.neibslist, n, ni, step, run_mode)
-        ext([self.vel])
+            self._exchange([self.gradgamma])
+        if not self.io:
+            return self._sa_bc(self._state_of(self.pos), step, run_mode)
+        # with open boundaries (:150-290): corner vertices, the initial masses of the open vertices, then the imposed values and
+        # the two condition passes of step 0
+        if step != 0 or run_mode != D.SIMULATE:
+            raise NotImplementedError("open boundaries: only the initialisation sequence goes through sa_boundary_conditions")
+        K.sa_identify_corner_vertices(self.pos, self.info, self.hash, self.vertices, self.cellStart, self.neibslist, n, ni)
+        self._exchange([self.info])
+        K.sa_init_io_mass_vertex_count(self.forces, self.pos, self.vertices, self.hash, self.info, self.cellStart, self.neibslist, n, ni)
+        self._exchange([self.forces])      # a vertex divides by the counts of the vertices it shares segments with, the halo's among them
+        K.sa_init_io_mass(self.pos2, self.pos, self.forces, self.vertices, self.hash, self.info, self.cellStart, self.neibslist, n, ni)
+        self.pos2[ni:n] = self.pos[ni:n]      # (the pass writes the internal rows)
+        self._swap("pos")
+        self._exchange([self.pos])
+        self._sa_bc_io(self._state_of(self.pos), 0.0, 0)
 
     def _update_segments_and_halo(self):
         """UPDATE_SEGMENTS + CROP + APPEND_EXTERNAL (src/Integrator.cc:170-230)"""
@@ -653,110 +647,98 @@ class MultiGpuEngine:
         """INIT_ / POSTPRED_ / POSTCORR_EFFPRES_PREP and the Jacobi loop behind it (PredictorCorrectorIntegrator.cc:962-1008,
         1046-1182) on the given state, as one call; the surface and interface flags are those the last
         postprocess(INTERFACE_DETECTION) left in INFO.  Synchronises (the iteration count comes back)."""
-        it, err, res = self.k.jacobi_solve(self.effpres, pos, vel, self.info, self.hash, self.cellStart, self.neibslist,
-                                           self.n_local, self.n_int)
+        it, err, res = self.k.jacobi_solve(self.effpres, pos, vel, *self._lists, self.n_local, self.n_int)
         self.jacobi_iterations[phase] = it
         self.jacobi_last[phase] = (err, res)
         self.jacobi_max_iterations = max(self.jacobi_max_iterations, it)
 
-    def _forces_pass(self, pos, vel, combine_min, run_mode=D.SIMULATE, step=1):
-        K = self.k
-        # (with bodies: rows of body particles owned by other ranks must read zero in the reduction)
-        K.memset(self._zeroed if self.has_rb else self.cfl, 0)
-        prof = self.profile_forces is not None and self.is_cuda
-        if prof:
-            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-        sps = self.sps and run_mode == D.SIMULATE
-        if sps:   # CALC_VISC on the state the forces read (PredictorCorrectorIntegrator.cc:460-480)
-            K.calc_visc(self.tau, pos, vel, self.info, self.hash, self.cellStart, self.neibslist, self.n_local, self.n_int,
-                        turbvisc=self.turbvisc)
-            if self.world > 1:
-                self._exchange(self.tau)
-        # the forces entry of this option set, as a function of the particle range and the offset into the CFL array
-        if self.sa:      # forces engine of SA_BOUNDARY: the state's gamma, the boundary elements, the vertex offsets of the segments
-            st = self._state_of(pos)      # ... its k-epsilon fields, its Eulerian velocities
-            ggam, be = st.gradgamma, st.boundelements
-            ke = st.ke if (self.keps and run_mode == D.SIMULATE) else None
+    # The forces entry of each option set.  _forces_<set>(pos, vel, step, run_mode) first computes what its entry reads beside the
+    # state, over the internal particles and with the UPDATE_EXTERNAL of it, and returns (launch, outputs): launch(from, to, offset
+    # into the CFL array) runs the entry on a range of particles and returns its blocks; `outputs` is what the entry writes beside
+    # BUFFER_FORCES that the halo copies integrate from.
+    def _forces_sa(self, pos, vel, step, run_mode):
+        """forces engine of SA_BOUNDARY: the state's gamma, the boundary elements, the vertex offsets of the segments, its k-epsilon
+        fields, its Eulerian velocities"""
+        K, st = self.k, self._state_of(pos)
+        ke = st.ke if (self.keps and run_mode == D.SIMULATE) else None
+        if ke is not None:
+            K.memset(self.cfl_keps, 0)
+        # bodies that feel the fluid (FG_COMPUTE_FORCE segments): the pressure force on their elements rides with the pass
+        # (compute_boundary_pressure_force inside finalizeforcesDevice, src/cuda/forces_kernel.def:4115-4145)
+        body_forces = self.has_rb and self.sp.numforcesbodies > 0 and run_mode == D.SIMULATE
+
+        def launch(frm, to, off):
             if ke is not None:
-                K.memset(self.cfl_keps, 0)
-            # bodies that feel the fluid (FG_COMPUTE_FORCE segments): the pressure force on their elements rides with the pass
-            # (compute_boundary_pressure_force inside finalizeforcesDevice, src/cuda/forces_kernel.def:4115-4145)
-            body_forces = self.has_rb and self.sp.numforcesbodies > 0 and run_mode == D.SIMULATE
-
-            def launch(frm, to, off):
-                nb = launch_sa(frm, to, off)
-                if body_forces:
-                    K.sa_body_pressure_forces(self.forces, self.rbforces, self.rbtorques, pos, vel, self.info, self.hash, be, frm, to)
-                return nb
-
-            def launch_sa(frm, to, off):
-                if ke is not None:
-                    return K.forces_sa_keps(self.forces, self.cfl, self.cfl_keps, self.dkde, pos, vel, self.info, self.hash, self.cellStart,
-                                            self.neibslist, ggam, self.boundelements, self.vertpos, ke, self.n_local, frm, to, off,
-                                            cfl_gamma=self.cfl_gamma)
-                if self.io:      # the Eulerian velocity of the open boundaries in the viscous terms and in the gamma CFL condition
-                    return K.forces_sa_io(self.forces, self.cfl, pos, vel, st.eulervel, self.info, self.hash, self.cellStart, self.neibslist, ggam,
-                                          be, self.vertpos, self.n_local, frm, to, off, cfl_gamma=self.cfl_gamma)
-                return K.forces_sa(self.forces, self.cfl, pos, vel, self.info, self.hash, self.cellStart, self.neibslist, ggam,
-                                   be, self.vertpos, self.n_local, frm, to, off, cfl_gamma=self.cfl_gamma, run_mode=run_mode)
-        elif self.effvisc_on and run_mode == D.SIMULATE:
-            # CALC_VISC on the state the forces read (internal particles, then UPDATE_EXTERNAL); its largest kinematic viscosity
-            # is the viscous limit of this pass's dt on this device (the dt of the step is the minimum over the devices)
-            if self.granular:      # the yield stress of the sediment comes from BUFFER_EFFPRES
-                K.calc_effvisc_granular(self.effvisc, self.effpres, pos, vel, self.info, self.hash, self.cellStart, self.neibslist,
-                                        self.n_local, self.n_int)
+                nb = K.forces_sa_keps(self.forces, self.cfl, self.cfl_keps, self.dkde, pos, vel, *self._lists, st.gradgamma,
+                                      self.boundelements, self.vertpos, ke, self.n_local, frm, to, off, cfl_gamma=self.cfl_gamma)
+            elif self.io:    # the Eulerian velocity of the open boundaries in the viscous terms and in the gamma CFL condition
+                nb = K.forces_sa_io(self.forces, self.cfl, pos, vel, st.eulervel, *self._lists, st.gradgamma, st.boundelements,
+                                    self.vertpos, self.n_local, frm, to, off, cfl_gamma=self.cfl_gamma)
             else:
-                K.calc_effvisc(self.effvisc, pos, vel, self.info, self.hash, self.cellStart, self.neibslist, self.n_local, self.n_int)
-            if self.world > 1:
-                self._exchange([self.effvisc])
+                nb = K.forces_sa(self.forces, self.cfl, pos, vel, *self._lists, st.gradgamma, st.boundelements, self.vertpos,
+                                 self.n_local, frm, to, off, cfl_gamma=self.cfl_gamma, run_mode=run_mode)
+            if body_forces:
+                K.sa_body_pressure_forces(self.forces, self.rbforces, self.rbtorques, pos, vel, self.info, self.hash, st.boundelements, frm, to)
+            return nb
+        # BUFFER_DKDE is a POST_FORCES_UPDATE_BUFFER: the halo copies integrate k and epsilon from the exchanged rates
+        return launch, ([] if ke is None else [self.dkde])
 
-            def launch(frm, to, off):
-                return K.forces_effvisc(self.forces, self.cfl, pos, vel, self.info, self.hash, self.cellStart, self.neibslist,
-                                        self.effvisc, self.n_local, frm, to, off)
-        elif self.grenier and run_mode == D.SIMULATE:
-            # COMPUTE_DENSITY on the state the forces read, UPDATE_EXTERNAL of sigma and of the rewritten velocity buffer
-            # (PredictorCorrectorIntegrator.cc:443-458), then the Grenier forces
-            K.compute_density(self.sigma, vel, pos, self.info, self.hash, self._state_of(pos).vol, self.cellStart, self.neibslist, self.n_int)
-            if self.world > 1:
-                self._exchange([self.sigma, vel])
-
-            def launch(frm, to, off):
-                return K.forces_grenier(self.forces, self.cfl, pos, vel, self.info, self.hash, self.cellStart, self.neibslist,
-                                        self.sigma, self.n_local, frm, to, off)
+    def _forces_effvisc(self, pos, vel, step, run_mode):
+        """generalized Newtonian rheology: CALC_VISC on the state the forces read; its largest kinematic viscosity is the viscous
+        limit of this pass's dt on this device (the dt of the step is the minimum over the devices)"""
+        K = self.k
+        if self.granular:      # the yield stress of the sediment comes from BUFFER_EFFPRES
+            K.calc_effvisc_granular(self.effvisc, self.effpres, pos, vel, *self._lists, self.n_local, self.n_int)
         else:
-            args = (self.forces, self.cfl, self.rbforces if self.has_rb else None, self.rbtorques if self.has_rb else None, pos, vel,
-                    self.info, self.hash, self.cellStart, self.neibslist, self.n_local)
-            kw = dict(tau=self.tau) if sps else {}
-            if self.xsph is not None:
-                kw["xsph"] = self.xsph
-            if run_mode != D.SIMULATE or step != 1:
-                kw.update(run_mode=run_mode, step=step)
-            vouch = [self._rows_follow and run_mode == D.SIMULATE and self._rows_for is not None and self._rows_for[0] is vel and
-                     vel._version == self._rows_for[1]]
+            K.calc_effvisc(self.effvisc, pos, vel, *self._lists, self.n_local, self.n_int)
+        self._exchange([self.effvisc])
+        return (lambda frm, to, off: K.forces_effvisc(self.forces, self.cfl, pos, vel, *self._lists, self.effvisc, self.n_local,
+                                                      frm, to, off)), []
 
-            def launch(frm, to, off):
-                if vouch[0]:
-                    K.eos_rows_current(vel, self.n_local)
-                vouch[0] = self._rows_follow and run_mode == D.SIMULATE      # a second stripe of this pass reads the buffer the first one read
-                return K.forces(*args, frm, to, off, **kw)
-        energy = self.energy_on and run_mode == D.SIMULATE      # the BUFFER_INTERNAL_ENERGY_UPD output of the pass travels with the forces
-        if energy:
-            K.forces_internal_energy(self.dedt, pos, vel, self.info, self.hash, self.cellStart, self.neibslist, self.n_local, 0, self.n_int)
-        outputs = [self.forces, self.dedt] if energy else [self.forces]
-        if self.xsph is not None and run_mode == D.SIMULATE:      # BUFFER_XSPH is a POST_FORCES_UPDATE_BUFFER: the halo copies are moved with it
-            outputs.append(self.xsph)
-        keps = self.keps and run_mode == D.SIMULATE
-        if keps:         # BUFFER_DKDE is a POST_FORCES_UPDATE_BUFFER: the halo copies integrate k and epsilon from the exchanged rates
-            outputs.append(self.dkde)
+    def _forces_grenier(self, pos, vel, step, run_mode):
+        """SPH_GRENIER: COMPUTE_DENSITY on the state the forces read, UPDATE_EXTERNAL of sigma and of the rewritten velocity buffer
+        (PredictorCorrectorIntegrator.cc:443-458), then the Grenier forces"""
+        K = self.k
+        K.compute_density(self.sigma, vel, pos, self.info, self.hash, self._state_of(pos).vol, self.cellStart, self.neibslist, self.n_int)
+        self._exchange([self.sigma, vel])
+        return (lambda frm, to, off: K.forces_grenier(self.forces, self.cfl, pos, vel, *self._lists, self.sigma, self.n_local,
+                                                      frm, to, off)), []
+
+    def _forces_plain(self, pos, vel, step, run_mode):
+        """the plain forces engine (and every engine's REPACK pass but SA's): SPS stresses, XSPH, the rows of the bodies"""
+        K = self.k
+        args = (self.forces, self.cfl, self.rbforces if self.has_rb else None, self.rbtorques if self.has_rb else None, pos, vel,
+                *self._lists, self.n_local)
+        kw = dict(tau=self.tau) if self.sps and run_mode == D.SIMULATE else {}
+        if self.xsph is not None:
+            kw["xsph"] = self.xsph
+        if run_mode != D.SIMULATE or step != 1:
+            kw.update(run_mode=run_mode, step=step)
+        follow = self._rows_follow and run_mode == D.SIMULATE
+        vouch = [follow and self._rows_for is not None and self._rows_for[0] is vel and vel._version == self._rows_for[1]]
+
+        def launch(frm, to, off):
+            if vouch[0]:
+                K.eos_rows_current(vel, self.n_local)
+            vouch[0] = follow      # a second stripe of this pass reads the buffer the first one read
+            return K.forces(*args, frm, to, off, **kw)
+        return launch, []
+
+    def _launch_stripes(self, launch, outputs, e0):
+        """`launch` over the internal particles, then the UPDATE_EXTERNAL of `outputs`; returns the blocks launched.  With a halo the
+        edge stripe goes first and its forces travel, on the exchange stream when overlapped, while the inner stripe computes.
+        `e0`: the event that opened an interval of profile_forces, or None."""
+        def profiled():
+            if e0 is not None:
+                e1 = torch.cuda.Event(enable_timing=True)
+                e1.record(); self.profile_forces.append((e0, e1))
         if self.world > 1 and self.n_int > self.edge_start:
             # edge stripe first, then the inner stripe while the edge forces travel
             nb1 = launch(self.edge_start, self.n_int, 0)
             if self.overlap:
                 ev = torch.cuda.Event(); ev.record()
             nb2 = launch(0, self.edge_start, nb1)
-            if prof:
-                e1.record(); self.profile_forces.append((e0, e1))
+            profiled()
             if self.overlap:
                 with torch.cuda.stream(self.comm_stream):
                     self.comm_stream.wait_event(ev)
@@ -769,94 +751,118 @@ class MultiGpuEngine:
                     a_.record(); self.exchange_events.append((b, a_))
             else:
                 self._exchange(outputs)
-        else:
-            nb1 = launch(0, self.n_int, 0)
-            nb2 = 0
-            if prof:
-                e1.record(); self.profile_forces.append((e0, e1))
-            if self.world > 1:
-                self._exchange(outputs)
-        K.dtreduce(self.cfl, self.cfl_temp, nb1 + nb2, self.d_dt_next, combine_min)
-        if keps:         # viscous limit with the largest eddy viscosity (src/cuda/forces.cu:585-598)
-            K.dtreduce_keps(self.cfl_keps, nb1 + nb2, self.d_dt_next)
-        if self.sa and self.sa_dynamic_gamma and run_mode == D.SIMULATE:     # the CFL condition of the gamma transport (src/cuda/forces.cu:576-585)
-            K.dtreduce_gamma(self.cfl_gamma, self.n_local, nb1 + nb2, self.d_dt_next)
+            return nb1 + nb2
+        nb = launch(0, self.n_int, 0)
+        profiled()
+        self._exchange(outputs)
+        return nb
+
+    def _forces(self, pos, vel, step, combine_min, run_mode=D.SIMULATE):
+        """One forces pass on the given state: CALC_VISC and what else the option set's entry reads (_forces_sa, _forces_effvisc,
+        _forces_grenier, _forces_plain), the entry over one stripe or two (_launch_stripes), then the reductions of this pass's dt
+        into d_dt_next (`combine_min`: the minimum with what the predictor's pass left there)."""
+        K, simulate = self.k, run_mode == D.SIMULATE
+        # (with bodies: rows of body particles owned by other ranks must read zero in the reduction)
+        K.memset(self._zeroed if self.has_rb else self.cfl, 0)
+        e0 = None
+        if self.profile_forces is not None and self.is_cuda:
+            e0 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+        if self.sps and simulate:   # CALC_VISC on the state the forces read (PredictorCorrectorIntegrator.cc:460-480)
+            K.calc_visc(self.tau, pos, vel, *self._lists, self.n_local, self.n_int, turbvisc=self.turbvisc)
+            self._exchange(self.tau)
+        entry = (self._forces_sa if self.sa else self._forces_effvisc if self.effvisc_on and simulate else
+                 self._forces_grenier if self.grenier and simulate else self._forces_plain)
+        launch, more = entry(pos, vel, step, run_mode)
+        outputs = [self.forces]
+        if self.energy_on and simulate:      # the BUFFER_INTERNAL_ENERGY_UPD output of the pass travels with the forces
+            K.forces_internal_energy(self.dedt, pos, vel, *self._lists, self.n_local, 0, self.n_int)
+            outputs.append(self.dedt)
+        if self.xsph is not None and simulate:      # BUFFER_XSPH is a POST_FORCES_UPDATE_BUFFER: the halo copies are moved with it
+            outputs.append(self.xsph)
+        nb = self._launch_stripes(launch, outputs + more, e0)
+        K.dtreduce(self.cfl, self.cfl_temp, nb, self.d_dt_next, combine_min)
+        if self.keps and simulate:         # viscous limit with the largest eddy viscosity (src/cuda/forces.cu:585-598)
+            K.dtreduce_keps(self.cfl_keps, nb, self.d_dt_next)
+        if self.sa and self.sa_dynamic_gamma and simulate:     # the CFL condition of the gamma transport (src/cuda/forces.cu:576-585)
+            K.dtreduce_gamma(self.cfl_gamma, self.n_local, nb, self.d_dt_next)
         if self.io and self.water_depth_on:      # the vertex pass of the forces (vertex_forces, src/cuda/forces.cu:676-686)
-            K.sa_io_water_depth(self.iowaterdepth, pos, self.info, self.hash, self.cellStart, self.neibslist, self.n_local, 0, self.n_int)
+            K.sa_io_water_depth(self.iowaterdepth, pos, *self._lists, self.n_local, 0, self.n_int)
+
+    def _euler(self, step, dt_scale, run_mode=D.SIMULATE):
+        """the EULER command of the plain integrator: the new positions and velocities from the state of step n and BUFFER_FORCES"""
+        kw = dict(xsph=self.xsph) if self.xsph is not None else {}
+        if run_mode != D.SIMULATE:
+            kw["run_mode"] = run_mode
+        self.k.euler(self.pos2, self.vel2, self.pos, self.vel, self.info, self.hash, self.forces, self.n_local, self.d_dt,
+                     dt_scale, step, **kw)
+
+    def apply_filter(self, filtertype):
+        """FILTER_CALL phase (src/integrators/PredictorCorrectorIntegrator.cc:831-859): read the unfiltered velocities, write the
+        filtered ones of the internal particles, UPDATE_EXTERNAL, swap the two VEL buffers."""
+        self._rows_for = None      # the velocity buffer may be rewritten behind torch's back (_rows_for)
+        self.k.filter(int(filtertype), self.vel2, self.pos, self.vel, *self._lists, self.n_local, self.n_int)
+        self._exchange([self.vel2])
+        self._swap("vel")
+
+    def _substep(self, step, dt_host=None):
+        """Predictor (step 1): forces(n) -> n* = n + dt/2 f.  Corrector (step 2): forces(n*) -> n+1 = n + dt f*, written over n*.
+        Every update integrates from the state of step n into the second copy of its buffer.  `dt_host`: dt for the bodies'
+        callback."""
+        K, n, dt_scale = self.k, self.n_local, (0.5 if step == 1 else 1.0)
+        pos, vel = (self.pos, self.vel) if step == 1 else (self.pos2, self.vel2)
+        self._forces(pos, vel, step, combine_min=step - 1)
+        if self.bodies is not None:                 # MOVE_BODIES + uploads (PredictorCorrectorIntegrator.cc:550-570)
+            self._last_motion = self.bodies.timestep(step, dt_host, self.t_host)
+            K.set_body_motion(self._last_motion, self.sp.numforcesbodies > 0)
+        if self.grenier:             # with the volumes, which the corrector overwrites like pos and vel
+            K.euler_grenier(self.pos2, self.vel2, self.vol2, self.pos, self.vel, self.vol, self.info, self.hash, self.forces, n, self.d_dt,
+                            dt_scale, step)
+        else:
+            self._euler(step, dt_scale)
+            self._rows_for = (self.vel2, self.vel2._version)
+        if self.sa_moving:           # update_normals of the Euler step: BUFFER_BOUNDELEMENTS of n* / n+1 from that of n
+            K.sa_update_normals(self.boundelements2, self.boundelements, self.info, n, n)
+        if self.energy_on:
+            K.euler_internal_energy(self.energy2, self.energy, self.dedt, self.pos, self.info, n, self.d_dt, dt_scale)
+        if self.keps:
+            K.euler_keps(self.ke2, self.ke, self.dkde, self.forces, self.pos, self.info, n, self.d_dt, dt_scale)
+        if self.io:                  # (in the corrector the particle count grows by the released particles: n is stale behind it)
+            self._sa_post_euler_io(step)
+        elif self.sa:
+            self._sa_post_euler(step)
+        if self.granular:            # POSTPRED_EFFPRES on n* (its result is the field of the state n as well), POSTCORR_EFFPRES on n+1
+            self._solve_effpres("predictor" if step == 1 else "corrector", self.pos2, self.vel2)
+
+    def _finish_step(self, written):
+        """TIME_STEP_EPILOGUE (GPUSPH.cc:650-657): the new state becomes the current one (`written`: the buffers that have a new copy),
+        t += dt, dt = min(dt_pred, dt_corr) over all devices"""
+        self._swap(*written)
+        self.k.time_advance(self.d_t, self.d_dt)
+        if self.world > 1:
+            self.transport.allreduce_min(self.d_dt_next)
+        self.d_dt, self.d_dt_next = self.d_dt_next, self.d_dt
+        self.iterations += 1
 
     def step(self):
-        K = self.k
         if self.iterations % self.sp.buildneibsfreq == 0:
             self.build_neibs()
             if self.sa and self.iterations == 0:     # initialisation step of the boundary conditions (not after a resume)
                 self.sa_boundary_conditions(0)
             if self.granular and self.iterations == 0:      # INIT_EFFPRES, after the first list build
                 self._solve_effpres("init", self.pos, self.vel)
-        n = self.n_local
-        if self.iterations > 0:      # FILTER phases: internal particles, then UPDATE_EXTERNAL of the velocity buffer
+        if self.iterations > 0:
             for ftype, freq in self.filters:
                 if self.iterations % freq == 0:
-                    self._rows_for = None
-                    K.filter(ftype, self.vel2, self.pos, self.vel, self.info, self.hash, self.cellStart, self.neibslist, n, self.n_int)
-                    if self.world > 1:
-                        self._exchange([self.vel2])
-                    self._swap("vel")
-        ekw = dict(xsph=self.xsph) if self.xsph is not None else {}
-        if self.bodies is not None:
-            dt_host = float(self.d_dt.item())       # the callback needs dt on the host: one synchronisation per step
-        # predictor: forces(step n) -> n* = n + dt/2 f
-        self._forces_pass(self.pos, self.vel, 0, step=1)
-        if self.bodies is not None:                 # MOVE_BODIES + uploads (PredictorCorrectorIntegrator.cc:550-570)
-            m = self.bodies.timestep(1, dt_host, self.t_host); K.set_body_motion(m, self.sp.numforcesbodies > 0)
-        if self.grenier:
-            K.euler_grenier(self.pos2, self.vel2, self.vol2, self.pos, self.vel, self.vol, self.info, self.hash, self.forces, n, self.d_dt, 0.5, 1)
-        else:
-            K.euler(self.pos2, self.vel2, self.pos, self.vel, self.info, self.hash, self.forces, n, self.d_dt, 0.5, 1, **ekw)
-            self._rows_for = (self.vel2, self.vel2._version)
-        if self.sa_moving:           # update_normals of the Euler step: BUFFER_BOUNDELEMENTS of n* from that of n
-            K.sa_update_normals(self.boundelements2, self.boundelements, self.info, n, n)
-        if self.energy_on:
-            K.euler_internal_energy(self.energy2, self.energy, self.dedt, self.pos, self.info, n, self.d_dt, 0.5)
-        if self.keps:
-            K.euler_keps(self.ke2, self.ke, self.dkde, self.forces, self.pos, self.info, n, self.d_dt, 0.5)
-        if self.io:
-            self._sa_post_euler_io(1)
-        elif self.sa:
-            self._sa_post_euler(1)
-        if self.granular:            # POSTPRED_EFFPRES on the state n*; its result is the field of the state n as well
-            self._solve_effpres("predictor", self.pos2, self.vel2)
-        # corrector: forces(step n*) -> n+1 = n + dt f*   (written over n*, then renamed to n)
-        self._forces_pass(self.pos2, self.vel2, 1, step=2)
-        if self.bodies is not None:
-            m = self.bodies.timestep(2, dt_host, self.t_host); K.set_body_motion(m, self.sp.numforcesbodies > 0)
-        if self.grenier:     # the volumes of n* are overwritten by those of n+1, like pos and vel
-            K.euler_grenier(self.pos2, self.vel2, self.vol2, self.pos, self.vel, self.vol, self.info, self.hash, self.forces, n, self.d_dt, 1.0, 2)
-        else:
-            K.euler(self.pos2, self.vel2, self.pos, self.vel, self.info, self.hash, self.forces, n, self.d_dt, 1.0, 2, **ekw)
-            self._rows_for = (self.vel2, self.vel2._version)
-        if self.sa_moving:           # ... of n+1 from that of n (the full step's rotation)
-            K.sa_update_normals(self.boundelements2, self.boundelements, self.info, n, n)
-        if self.energy_on:
-            K.euler_internal_energy(self.energy2, self.energy, self.dedt, self.pos, self.info, n, self.d_dt, 1.0)
-        if self.keps:
-            K.euler_keps(self.ke2, self.ke, self.dkde, self.forces, self.pos, self.info, n, self.d_dt, 1.0)
-        if self.io:
-            self._sa_post_euler_io(2)        # (the particle count has grown by the released particles: n is stale from here on)
-        elif self.sa:
-            self._sa_post_euler(2)
-        if self.granular:            # POSTCORR_EFFPRES on the state n+1
-            self._solve_effpres("corrector", self.pos2, self.vel2)
+                    self.apply_filter(ftype)
+        # (the bodies' callback needs dt on the host: one synchronisation per step)
+        dt_host = float(self.d_dt.item()) if self.bodies is not None else None
+        self._substep(1, dt_host)
+        self._substep(2, dt_host)
         if self.bodies is not None:                 # EULER_UPLOAD_OBJECTS_CG in the post-corrector phase (:331-332)
-            K.set_body_cg_integration(m)
-            self._last_motion = m
+            self.k.set_body_cg_integration(self._last_motion)
             self.t_host += dt_host                  # the same double += float as on the device
-        self._swap(*self._stepped)      # n+1 becomes n: every buffer the step wrote a new copy of (BUFFERS)
-        # TIME_STEP_EPILOGUE: t += dt ; dt = min(dt_pred, dt_corr), over all devices (GPUSPH.cc:650-657)
-        K.time_advance(self.d_t, self.d_dt)
-        if self.world > 1:
-            self.transport.allreduce_min(self.d_dt_next)
-        self.d_dt, self.d_dt_next = self.d_dt_next, self.d_dt
-        self.iterations += 1
+        self._finish_step(self._stepped)            # every buffer the step wrote a new copy of (BUFFERS)
 
     def run(self, steps):
         for _ in range(steps):
@@ -901,8 +907,8 @@ class MultiGpuEngine:
     def detect_surface(self, normals=None):
         """SURFACE_DETECTION of the rows this rank owns (their lists reach into the halo): FG_SURFACE in INFO, in place"""
         pp = self.problem.physparams
-        self.k.postprocess(D.SURFACE_DETECTION, None, None, self.info, normals, self.pos, self.vel, self.info, self.hash, self.cellStart,
-                           self.neibslist, self.n_int, getattr(pp, "cosconeanglefluid", 0.86), getattr(pp, "cosconeanglenonfluid", 0.5))
+        self.k.postprocess(D.SURFACE_DETECTION, None, None, self.info, normals, self.pos, self.vel, *self._lists, self.n_int,
+                           getattr(pp, "cosconeanglefluid", 0.86), getattr(pp, "cosconeanglenonfluid", 0.5))
         self._surface_for = self._state_key()
 
     def wave_gages(self, gages=None):
