@@ -178,7 +178,7 @@ grenier_forces_kernel(DevParams p, GrenierForcesArgs a)
 			force.w /= a.sigma[index];
 			if (fluid) {
 				force.x += p.gravity[0]; force.y += p.gravity[1]; force.z += p.gravity[2];
-				// GeometryForce / PlaneForce (src/cuda/forces_kernel.cu:140-203), as in forces.hip finalize_particle
+				// GeometryForce / PlaneForce (src/cuda/forces_kernel.cu:140-203), as in forces_pair.h finalize_particle
 				if ((p.simflags & SPHX_ENABLE_PLANES) && p.numplanes) {
 					for (uint32_t k = 0; k < p.numplanes; ++k) {
 						const float ddx = (gridPos.x - p.plane_gridpos[k][0])*p.cs[0] + (pos.x - p.plane_pos[k][0]);

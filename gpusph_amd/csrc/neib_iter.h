@@ -26,7 +26,7 @@ __device__ __forceinline__ float kernel_W(const DevParams &p, float r)
 	return val*p.wcoeff;
 }
 
-// F<kerneltype>(r, h) = (1/r) dW/dr: src/cuda/sph_core.cu:140-215 (same forms as kernel_F of forces.hip, IEEE division)
+// F<kerneltype>(r, h) = (1/r) dW/dr: src/cuda/sph_core.cu:140-215 (same forms as kernel_F of forces_pair.h, IEEE division)
 template<int KERNEL>
 __device__ __forceinline__ float gn_kernel_F(const DevParams &p, float r)
 {

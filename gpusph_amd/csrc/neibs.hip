@@ -5,7 +5,7 @@
 //
 // Numerics (DESIGN.md "Numerics"): compiled with -ffp-contract=off; `a - b*c` shapes are
 // explicit fmaf, squared lengths are fmaf(z,z,fmaf(y,y,x*x)), division is IEEE.
-#include "sphx_internal.h"
+#include "tile_format.h"
 #include <cstring>
 
 #define BLOCK_HASH    256
@@ -382,7 +382,7 @@ cell_fluid_end_kernel(uint32_t *__restrict__ cellFluidEnd, const uint32_t *__res
 }
 
 // ------------------------------------------------------------------------------------------
-// forces tiles (consumed by forces_tile_kernel, forces.hip).  A tile is a block of k x 2 x 2 cells
+// forces tiles (consumed by forces_tile_kernel, forces_tile.h; descriptor words: tile_format.h).  A tile is a block of k x 2 x 2 cells
 // (k consecutive cells along COORD1 in each of 4 adjacent grid rows) holding <= TILE_PMAX
 // particles; its neighbour window is the (k+2) x 4 x 4 block around it (16 contiguous particle
 // ranges) and must fit TILE_WCAP records.  One thread per 2x2 bundle of rows walks the cells along
@@ -468,9 +468,9 @@ build_tiles_kernel(DevParams p, const uint32_t *__restrict__ cellStart, const ui
 		const uint32_t idx = atomicAdd(&ctl[0], 1u);
 		if (idx >= capacity) { ctl[1] = 1u; return; }
 		uint32_t *d = tiles + (size_t)TILE_DESC*idx;
-		d[0] = (uint32_t)g2; d[1] = (uint32_t)g3; d[2] = (uint32_t)ca; d[3] = (uint32_t)ncells;
-		for (int r = 0; r < TILE_HROWS; ++r) { d[4 + r] = first[r]; d[8 + r] = hc[r]; }
-		d[12] = wc; d[13] = fl; d[14] = 0u; d[15] = 0u;
+		d[TILE_D_G2] = (uint32_t)g2; d[TILE_D_G3] = (uint32_t)g3; d[TILE_D_FIRSTCELL] = (uint32_t)ca; d[TILE_D_NCELLS] = (uint32_t)ncells;
+		for (int r = 0; r < TILE_HROWS; ++r) { d[TILE_D_FIRST + r] = first[r]; d[TILE_D_COUNT + r] = hc[r]; }
+		d[TILE_D_WINDOW] = wc; d[TILE_D_FLAGS] = fl; d[TILE_D_LISTBASE] = 0u; d[TILE_D_LANEBASE] = 0u;
 	};
 
 	uint32_t hsum = 0, wc = 0, wfl = 0;
@@ -766,7 +766,7 @@ static hipStream_t sphx_side_stream(sphx_ctx *ctx)
 	return ctx->side_stream;
 }
 
-// does this build tile the sorted particles for the forces engine (forces.hip "Tiled path")?  The options (sphx_tiles_opts_build),
+// does this build tile the sorted particles for the forces engine (forces_tile.h "Tiled path")?  The options (sphx_tiles_opts_build),
 // the switch, and a grid whose columns fit the tile_cols allocation (degenerate 1-D grids: generic kernels)
 static bool tiling_wanted(const sphx_ctx *ctx)
 {

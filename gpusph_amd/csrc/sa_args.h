@@ -66,7 +66,7 @@ struct SaForcesArgs {
 	float *dkde;          // BUFFER_DKDE: 3 floats per particle (diffusion term of k, of epsilon, Yap's C_e2)
 	float *cflKeps;       // BUFFER_CFL_KEPS: one per block
 	float epsilon;
-	// the tiled kernel (forces.hip, SPHX_TURB_SA) has left the fluid <- fluid and fluid <- vertex sums in FORCES: only the
+	// the tiled kernel (forces_tile.h, SPHX_TURB_SA) has left the fluid <- fluid and fluid <- vertex sums in FORCES: only the
 	// boundary elements and the fix-ups remain -- unless the tiling overflowed (*tileGuard != 0: the tiled kernel did nothing)
 	int tiled;
 	const uint32_t *tileGuard;

@@ -184,7 +184,7 @@ int sphx_ensure_tile_lists(sphx_ctx *ctx)
 	const size_t batches = n*5u/8u + 262144u;
 	const size_t lanes = 2u*n + 262144u;
 	if (batches >= ((size_t)1 << 31) || lanes >= ((size_t)1 << 31)) return SPHX_OK;      // 32-bit cursors
-	// the ring of the walk reads TILE_AHEAD batches past the end of a wave's share without a clamp (acc_load_at, forces.hip): those
+	// the ring of the walk reads TILE_AHEAD batches past the end of a wave's share without a clamp (acc_load_at, tile_ring.h): those
 	// batches are allocated behind the capacity the tiling may fill, so a stream filled to the last batch still reads its own memory
 	bool ok = hipMalloc((void**)&ctx->tile_list, sizeof(uint2)*64u*(batches + TILE_AHEAD)) == hipSuccess;
 	ok = ok && hipMalloc((void**)&ctx->tile_runs, sizeof(uint32_t)*TILE_RUNTAB*(size_t)ctx->tile_capacity) == hipSuccess;

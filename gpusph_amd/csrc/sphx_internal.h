@@ -33,15 +33,14 @@ enum { PT_FLUID = 0, PT_BOUNDARY = 1, PT_VERTEX = 2, PT_TESTPOINT = 3, PT_NONE =
 
 #define SPHX_BLOCK_FORCES 128   // one CFL entry per 128 particles (getFmaxElements contract)
 
-// forces tiles (see forces.hip "Tiled path"): a tile is a k x 2 x 2 block of cells (k along COORD1)
-#ifndef TILE_THREADS
+// forces tiles (see forces_tile.h "Tiled path"): a tile is a k x 2 x 2 block of cells (k along COORD1).  The capacities are here;
+// what the words of the tiling's tables mean is in tile_format.h
 #define TILE_THREADS  512                  // threads of the tiled kernel's workgroup: 8 waves, two per SIMD
 #define TILE_PMAX     640                  // home particles per tile: ten chunks of 64, dealt out to the eight waves batch by batch
 #define TILE_WCAP     2876                 // window records that fit LDS (48 B each, 1 workgroup per CU) next to the partial sums and the lane records
 #define TILE_WCAP_SPS 1720                 // ... with the SPS stress tensor of every window particle (80 B each)
 #define TILE_WCAP_SPS1 2156                // ... of an SPS run with one fluid (64 B each: no EOS rows, see tau_pack_kernel)
 #define TILE_WGS_PER_CU 1                  // persistent workgroups per CU (LDS bound)
-#endif
 #define SA_WALL_CACHE_ENTRIES 96           // boundary-section entries per wall particle whose |grad gamma_as| is kept (more: recomputed)
 #define TILE_HROWS    4                    // home rows: 2 (COORD2) x 2 (COORD3)
 #define TILE_WROWS    16                   // window rows: 4 x 4
@@ -51,19 +50,9 @@ enum { PT_FLUID = 0, PT_BOUNDARY = 1, PT_VERTEX = 2, PT_TESTPOINT = 3, PT_NONE =
 #define TILE_RUNS_MAX (TILE_CHUNKS + TILE_WAVES - 1)   // runs of a tile: a run is a stretch of ONE chunk's list batches walked by ONE wave
 #define TILE_MAXCELLS 14                   // cells per tile along COORD1
 #define TILE_KW       16                   // window columns (TILE_MAXCELLS + 2)
-#define TILE_DESC     16                   // uint32 per tile: g2, g3, firstCell, numCells, first[4], count[4], window, flags (build_tiles_kernel),
-                                           // first batch of its list stream, first entry of its lane tables (tile_lists_kernel)
-#define TILE_ROWDESC  32                   // uint32 per tile (tile_rows, written by tile_lists_kernel): first record of each of the 16
-                                           // window rows, then records per row and window slot of the row's first record as uint16 pairs
-// uint32 per tile of the run table (tile_runs, tile_lists_kernel): who walks what.
-//   [w], w < 8        wave w: first run | runs << 5 | first batch (tile-relative) << 10 | batches << 22
-//   [8]               chunks | home particles << 8 | runs << 24
-//   [9 + c], c < 10   chunk c: first run | runs << 8   (its partial sums, in list order)
-//   [24 + r], r < 17  run r: chunk | batches of the fluid section << 4 | batches of the second section << 12 | TILE_RUN_LAST if it ends its chunk
-#define TILE_RUNTAB   48
-#define TILE_RUN_LAST (1u << 20)
-#define TILE_RT_CHUNK 9
-#define TILE_RT_RUN   24
+#define TILE_DESC     16                   // uint32 per tile of the descriptors (tiles) ...
+#define TILE_ROWDESC  32                   // ... of the window rows (tile_rows) ...
+#define TILE_RUNTAB   48                   // ... and of the run table (tile_runs): the words are tile_format.h's
 #define TILE_NB       4                    // neighbours per batch in the tiled pair loop
 #define TILE_AHEAD    4                    // list batches kept in flight (register ring)
 
@@ -197,7 +186,7 @@ struct sphx_ctx {
 	uint32_t   *cell_end_copy; // [cells] cellEnd of the build the tiles belong to
 	uint32_t   *cell_fluid_end;// [cells] first non-fluid particle of each cell (neighbour-list build)
 	uint32_t   *neib_counts;   // [n] entries of the fluid section | entries of the second section << 16 of every list (build_neibs_kernel)
-	// tile lists (forces.hip "Tile lists"): the neighbour lists of the tiled particles as the tiled kernel walks them -- one
+	// tile lists (forces_tile.h "Tile lists"): the neighbour lists of the tiled particles as the tiled kernel walks them -- one
 	// stream of 512-byte batches (64 lanes x 4 window offsets) per tile, in the order its waves consume them
 	uint2      *tile_list;     // [tile_list_batches][64]
 	uint32_t    tile_list_batches;
@@ -322,7 +311,7 @@ static inline bool sphx_tiles_opts_build(const sphx_ctx *ctx)      // sphx_build
 }
 static inline bool sphx_tiles_opts_forces(const DevParams &d)      // sphx_forces_basicstep (DYN / LJ / MK boundaries)
 {
-	// more than one fluid or Ferrari diffusion: tiled for the Wendland kernel only (launch_forces_k, forces.hip)
+	// more than one fluid or Ferrari diffusion: tiled for the Wendland kernel only (launch_forces_k, forces_part.hip)
 	return ((d.numfluids == 1 && d.densitydiff != SPHX_FERRARI) || d.kerneltype == SPHX_WENDLAND) && d.formulation == SPHX_SPH_F1;
 }
 static inline bool sphx_tiles_opts_sa(const DevParams &d, int mode)      // sphx_sa_tiles_run; k-epsilon: the passes that do not involve the model

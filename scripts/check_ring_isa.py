@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""ISA check of the hand-managed list ring of forces_tile_kernel (gpusph_amd/csrc/forces.hip, "AccRing").
+"""ISA check of the hand-managed list ring of forces_tile_kernel (gpusph_amd/csrc/tile_ring.h, "AccRing").
 
 The list batches in flight live in the accumulation registers a0..a15, written and read by asm statements only: the compiler
 never sees a value that has not landed.  That holds as long as the compiler itself leaves those registers alone; every ring
@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gpusph_amd", "csrc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
          "-ffp-contract=off", "-fno-slp-vectorize", "--cuda-device-only", "-S"]
-PARTS = [["-DSPHX_FORCES_PART=%d" % k] for k in (1, 2, 3, 4)] + [["-DSPHX_FORCES_PART=3", "-DSPHX_FORCES_SA"]]
+PARTS = [["-DSPHX_FORCES_PART=%d" % k, "forces_part.hip"] for k in (1, 2, 3, 4)] + [["forces_sa.hip"]]      # flags, then the source
 ALLOWED_READERS = ("v_and_b32", "v_lshrrev_b32", "v_bfe_u32", "v_and_b32_sdwa", "v_lshrrev_b32_sdwa", "v_add_u32", "v_lshl_add_u32",
                    "v_and_or_b32", "v_add_lshl_u32", "v_mad_u32_u24", "v_mul_u32_u24", "v_lshlrev_b32")
 
@@ -117,7 +117,7 @@ def main():
         procs = []
         for k, extra in enumerate(PARTS):
             out = os.path.join(tmp, "part%d.s" % k)
-            procs.append((out, subprocess.Popen(["/opt/rocm/bin/hipcc"] + FLAGS + extra + [os.path.join(CSRC, "forces.hip"), "-o", out],
+            procs.append((out, subprocess.Popen(["/opt/rocm/bin/hipcc"] + FLAGS + extra[:-1] + [os.path.join(CSRC, extra[-1]), "-o", out],
                                                 stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)))
         for out, pr in procs:
             if pr.wait() != 0:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """hipcc with the accumulation-register budget of the device kernels stated instead of guessed.
 
-The tiled forces kernel keeps its list ring in a0..a15 by inline asm (forces.hip, "AccRing").  LLVM's register budget for
+The tiled forces kernel keeps its list ring in a0..a15 by inline asm (tile_ring.h, "AccRing").  LLVM's register budget for
 gfx90a+ is one file of VGPRs and AGPRs; a kernel whose IR does not say how many AGPRs it needs gets HALF of the budget as
 AGPRs as soon as anything names one (SIRegisterInfo::getMaxNumVectorRegs: "amdgpu-agpr-alloc" absent -> MaxVectorRegs / 2).
 With two waves per SIMD that is 128 + 128, the kernel's ~220 live values do not fit 128 and ~90 of them live in AGPR spill

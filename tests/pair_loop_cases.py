@@ -1,5 +1,5 @@
 """The runs that tests/test_gpu_pair_loop_bits.py compares and tests/golden/make_pair_loop_golden.py records: the plain tiled forces
-pass (Wendland kernel, artificial viscosity, one fluid, Colagrossi diffusion: pair_interact_pk in csrc/forces.hip) of a small dam
+pass (Wendland kernel, artificial viscosity, one fluid, Colagrossi diffusion: pair_interact_pk in csrc/forces_tile.h) of a small dam
 break under four gravities.  TEST INFRASTRUCTURE; needs a device.
 
 The pass has two instantiations: one for a gravity along z, whose g.r is the one product g_z r_z, and one for any gravity.  The host

@@ -1,6 +1,6 @@
 """All four SPH kernel functions through every engine they reach on the device.
 
-The kernel function is a compile-time axis of almost every pair loop (forces.hip, filters.hip, energy.hip, rheology.hip, granular.hip);
+The kernel function is a compile-time axis of almost every pair loop (forces_pair.h, filters.hip, energy.hip, rheology.hip, granular.hip);
 the rest of the suite launches it with a kernel other than Wendland in a handful of places.  Here every engine runs with the cubic
 spline, the quadratic, the Wendland (the CONTROL of every test: if its row fails, the harness is wrong and not a kernel) and the
 Gaussian kernel.  The Gaussian is the NARROW one of tests/kernel_axis.py (smoothing factor 1.0): the only Gaussian problem of the suite

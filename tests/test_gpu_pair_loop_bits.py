@@ -1,4 +1,4 @@
-"""The plain tiled forces pass has a second instantiation for a gravity along z (pair_interact_pk in csrc/forces.hip: g.r as the one
+"""The plain tiled forces pass has a second instantiation for a gravity along z (pair_interact_pk in csrc/forces_tile.h: g.r as the one
 product g_z r_z instead of a multiply and two FMAs).  It may change no bit:
 
   a. a context on it against a context kept on the instantiation for any gravity (sphx_dbg_forces_general_gravity), for gravity
