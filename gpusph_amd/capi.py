@@ -51,6 +51,9 @@ SIGNATURES = {
     "sphx_set_rb_cg_integration": (_i, [_vp, _vp, _vp, _i]),
     "sphx_set_rb_start": (_i, [_vp, _vp, _i]),
     "sphx_set_rb_motion": (_i, [_vp, _vp, _vp, _vp, _vp, _i]),
+    "sphx_floating_setup": (_i, [_vp, _i] + [_vp] * 7),
+    "sphx_floating_move": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "sphx_floating_state": (_i, [_vp, _vp, _vp, _vp]),
     "sphx_calc_hash": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "sphx_fix_hash": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "sphx_sort": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),

@@ -2,6 +2,7 @@
 #include "sphx_internal.h"
 #include "gages.h"
 #include "diagnostics.h"
+#include "floating.h"
 #include <cstdio>
 #include <cmath>
 #include <cstring>
@@ -117,6 +118,7 @@ extern "C" void sphx_destroy(sphx_ctx *ctx)
 	if (ctx->open_rows) (void)hipFree(ctx->open_rows);
 	sphx_gage_scratch_release(ctx);
 	sphx_diag_scratch_release(ctx);
+	sphx_floating_release(ctx);
 	free_granular(ctx);
 	delete ctx->forces_events;
 	delete ctx;
@@ -508,10 +510,15 @@ int sphx_rb_flush(sphx_ctx *ctx, hipStream_t st)
 	if (ctx->rb_ring > SPHX_RB_RING)      // the slot was used before: its copy must have executed before it is overwritten
 		SPHX_HIP(hipEventSynchronize(ctx->rb_staged[k]));
 	ctx->rb_staging[k] = ctx->rb_host;
-	SPHX_HIP(hipMemcpyAsync(ctx->rb_dev, &ctx->rb_staging[k], sizeof(RbParams), hipMemcpyHostToDevice, st));
+	// floating bodies (floating.hip): slots 0 .. numfloating-1 are written by the device, so the host's table lands in a second
+	// image and a one-wave kernel takes the other bodies' slots from there.  Without floating bodies: the one copy
+	FloatingEntry *fl = sphx_floating_entry(ctx);
+	const bool merge = fl && fl->numfloating > 0 && !fl->whole_upload;
+	SPHX_HIP(hipMemcpyAsync(merge ? fl->rb_image : ctx->rb_dev, &ctx->rb_staging[k], sizeof(RbParams), hipMemcpyHostToDevice, st));
 	SPHX_HIP(hipEventRecord(ctx->rb_staged[k], st));
 	ctx->rb_dirty = false;
-	return SPHX_OK;
+	if (fl) fl->whole_upload = false;
+	return merge ? fl->merge(ctx, fl, st) : SPHX_OK;
 }
 
 static int set_rb_cg(sphx_ctx *ctx, const int32_t *cgGridPos, const float *cgPos, int numbodies, bool forces, bool euler)

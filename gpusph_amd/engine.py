@@ -199,7 +199,15 @@ class TimestepEngine(MultiGpuEngine):
         if self.num_bodies_parts:
             pr = self.problem
             nb = len(pr.rb_firstindex)
-            for b in range(nb):
+            fstate = self.floating_state() if self.floating else None
+            rowstart = getattr(pr, "rb_rowstart", None)
+            for b in range(len(self.floating)):      # MB_FLOATING records from the device state, orientation included
+                s, fb = fstate[b], self.floating[b]
+                rows = int(rowstart[b + 1]) - int(rowstart[b])
+                bodies.append(dict(index=b, id=b, type=hotfile.MB_FLOATING, numparts=rows, firstindex=int(pr.rb_firstindex[b]),
+                                   lastindex=rows - 1, crot=s[0:3], orientation=s[3:7], lvel=s[7:10], avel=s[10:13],
+                                   initial_crot=fb.crot, initial_lvel=fb.lvel, initial_avel=fb.avel, initial_orientation=fb.orientation))
+            for b in range(len(self.floating), nb):
                 first = int(pr.rb_firstindex[b])
                 forces_body = self.sp.numforcesbodies > b
                 if self.bodies is not None:
@@ -267,9 +275,28 @@ class TimestepEngine(MultiGpuEngine):
             for b in range(nb):
                 gp[b], lp[b] = self.bodies.grid_and_local(self.bodies.kdata[b].crot)
             capi.check(self.lib.sphx_set_rb_cg(self.ctx.handle, gp.ctypes.data, lp.ctypes.data, nb))
+        if self.floating:      # MB_FLOATING records: the device state is set again from them (mass and inertia are the problem's)
+            from .bodies import FloatingBody
+            recs = {int(r["index"]): r for r in hf["bodies"]}
+            restored = []
+            for b, fb in enumerate(self.floating):
+                r = recs[b]
+                if int(r["type"]) != hotfile.MB_FLOATING:
+                    raise capi.SphxError("body %d of the HotFile is not a floating body" % b)
+                restored.append(FloatingBody(mass=fb.mass, inertia=fb.inertia, crot=np.array(r["crot"]), orientation=np.array(r["orientation"]),
+                                             lvel=np.array(r["lvel"]), avel=np.array(r["avel"])))
+            self.k.floating_setup(restored, np.asarray(self.problem.rb_rowstart, dtype=np.uint32))
         if self.iterations % self.sp.buildneibsfreq != 0:
             self.build_neibs()      # a resumed run always starts with a neighbour phase (GPUSPH::runSimulation)
         return hf
+
+    def floating_state(self, slots=False):
+        """The floating bodies as the device holds them: float64 [bodies, 19] -- centre of rotation (3), orientation (4: w, x, y, z),
+        linear velocity (3), angular velocity (3, world frame), total force (3) and torque (3) of the last substep -- and, with
+        slots=True, a dict of the bodies' rows of the rigid-body table as well.  Synchronises."""
+        if not self.floating:
+            raise ValueError("the problem has no floating bodies")
+        return self.k.floating_state(slots)
 
     def reduce_rb_forces(self):
         """REDUCE_BODIES_FORCES for the single obstacle body through the library's reduction; returns (force3, torque3)."""

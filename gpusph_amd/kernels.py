@@ -63,6 +63,36 @@ class HipKernels:
     def set_body_cg_integration(self, m):
         capi.check(self.lib.sphx_set_rb_cg_integration(self.ctx.handle, m["cg_grid"].ctypes.data, m["cg_pos"].ctypes.data, len(m["trans"])))
 
+    # ---- floating bodies (csrc/floating.hip): bodies 0 .. len(bodies)-1, moved on the device
+    FLOATING_STATE_DOUBLES, FLOATING_SLOT_WORDS = 19, 30
+
+    def floating_setup(self, bodies, rowstart):
+        """`bodies`: bodies.FloatingBody (or anything with mass, inertia, crot, orientation, lvel, avel); rowstart: len + 1 rows"""
+        nf = len(bodies)
+        col = lambda name, m: np.ascontiguousarray([np.asarray(getattr(b, name), dtype=np.float64).reshape(m) for b in bodies],
+                                                   dtype=np.float64).reshape(nf, m)
+        mass = np.ascontiguousarray([float(b.mass) for b in bodies], dtype=np.float64)
+        arrs = [mass, col("inertia", 3), col("crot", 3), col("orientation", 4), col("lvel", 3), col("avel", 3),
+                np.ascontiguousarray(rowstart, dtype=np.uint32)]
+        capi.check(self.lib.sphx_floating_setup(self.ctx.handle, nf, *[a.ctypes.data for a in arrs]))
+        self.num_floating = nf
+
+    def floating_move(self, rbforces, rbtorques, step, d_dt):
+        capi.check(self.lib.sphx_floating_move(self.ctx.handle, capi.ptr(rbforces), capi.ptr(rbtorques), int(step), capi.ptr(d_dt), self._s()))
+
+    def floating_state(self, slots=False):
+        """-> state (nf, 19) float64 [, slots: dict of the bodies' rows of the rigid-body table]; synchronises"""
+        nf = self.num_floating
+        state = np.zeros((nf, self.FLOATING_STATE_DOUBLES), dtype=np.float64)
+        raw = np.zeros((nf, self.FLOATING_SLOT_WORDS), dtype=np.float32)
+        capi.check(self.lib.sphx_floating_state(self.ctx.handle, state.ctypes.data, raw.ctypes.data if slots else None, self._s()))
+        if not slots:
+            return state
+        cells = raw[:, 24:].view(np.int32)
+        return state, dict(trans=raw[:, 0:3].copy(), rot=raw[:, 3:12].copy(), lvel=raw[:, 12:15].copy(), avel=raw[:, 15:18].copy(),
+                           cg_pos=raw[:, 18:21].copy(), cg_pos_e=raw[:, 21:24].copy(), cg_grid=cells[:, 0:3].copy(),
+                           cg_grid_e=cells[:, 3:6].copy())
+
     # ---- helpers
     def _s(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)

@@ -167,6 +167,20 @@ class MultiGpuEngine:
         # have never run
         if self.sa and self.sp.sph_formulation == D.SPH_HA and world > 1:
             raise NotImplementedError("SPH_HA with SA_BOUNDARY is built for a single domain")
+        # floating bodies (bodies 0 .. len-1): their dynamics run on the device (csrc/floating.hip); what is not built is refused
+        self.floating = list(getattr(problem, "floating_bodies", None) or ())
+        if self.floating:
+            if world > 1:
+                raise NotImplementedError("floating bodies are built for a single domain (the bodies' rows are not reduced across ranks)")
+            if self.sa:
+                raise NotImplementedError("floating bodies with SA_BOUNDARY are not built")
+            if self.grenier:
+                raise NotImplementedError("floating bodies with SPH_GRENIER are not built")
+            if self.sp.rheologytype == D.GRANULAR:
+                raise NotImplementedError("floating bodies with the GRANULAR rheology are not built")
+            if len(self.floating) > self.sp.numforcesbodies:
+                raise ValueError("%d floating bodies, but only %d bodies whose forces are computed (numforcesbodies)"
+                                 % (len(self.floating), self.sp.numforcesbodies))
         self.part = SlabPartition(problem, world)
         arrs = problem.copy_to_array()
         mask = self.part.local_mask(rank, arrs["hash"]) if world > 1 else np.ones(len(arrs["hash"]), dtype=bool)
@@ -323,8 +337,13 @@ class MultiGpuEngine:
         self.bodies = None
         if getattr(problem, "moving_bodies_callback", None) is not None and getattr(problem, "num_obstacle", 0):
             from .bodies import MovingBodies
-            self.bodies = MovingBodies(problem, problem.rb_cg_global)
+            self.bodies = MovingBodies(problem, problem.rb_cg_global, first=len(self.floating))
         self.t_host = 0.0
+        if self.floating:            # the device takes over their slots of the rigid-body table; rows of RB_FORCES per body
+            rowstart = np.asarray(problem.rb_rowstart, dtype=np.uint32)
+            if len(rowstart) != len(self.floating) + 1 or int(rowstart[-1]) > self.rbforces.shape[0]:
+                raise ValueError("rb_rowstart: one entry per floating body and one behind, inside the %d RB_FORCES rows" % self.rbforces.shape[0])
+            self.k.floating_setup(self.floating, rowstart)
 
     # ------------------------------------------------------------------ state buffers (BUFFERS)
     def _init_next_ids(self, arrs, mask, n0):
@@ -815,6 +834,8 @@ class MultiGpuEngine:
         if self.bodies is not None:                 # MOVE_BODIES + uploads (PredictorCorrectorIntegrator.cc:550-570)
             self._last_motion = self.bodies.timestep(step, dt_host, self.t_host)
             K.set_body_motion(self._last_motion, self.sp.numforcesbodies > 0)
+        if self.floating:                           # ... of the floating bodies, on the device and behind the host's uploads
+            K.floating_move(self.rbforces, self.rbtorques, step, self.d_dt)
         if self.grenier:             # with the volumes, which the corrector overwrites like pos and vel
             K.euler_grenier(self.pos2, self.vel2, self.vol2, self.pos, self.vel, self.vol, self.info, self.hash, self.forces, n, self.d_dt,
                             dt_scale, step)
@@ -855,7 +876,7 @@ class MultiGpuEngine:
             for ftype, freq in self.filters:
                 if self.iterations % freq == 0:
                     self.apply_filter(ftype)
-        # (the bodies' callback needs dt on the host: one synchronisation per step)
+        # (the callback of bodies with prescribed motion needs dt on the host: one synchronisation per step; floating bodies need none)
         dt_host = float(self.d_dt.item()) if self.bodies is not None else None
         self._substep(1, dt_host)
         self._substep(2, dt_host)

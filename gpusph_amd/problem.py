@@ -76,6 +76,7 @@ class Problem:
         self.parts = None
         self.planes = []            # [(unit normal (3), reference point (3), global coordinates)], PlaneList
         self.moving_bodies_callback = None   # ProblemCore::moving_bodies_callback: f(index, t0, t1, initial_kdata, kdata) -> (dx, dr)
+        self.floating_bodies = []            # bodies.FloatingBody of the GT_FLOATING_BODY geometries: body indices 0 .. len-1
         self.m_maxFall = float("nan")        # ProblemAPI<1>::setMaxFall
         self.gages = []                      # SimParams::gage (GageList): [x, y, z (output), smoothing length]
 
@@ -1550,3 +1551,126 @@ class LithostaticColumn(Problem):
 
     def initial_density(self, pos_global):
         raise NotImplementedError("LithostaticColumn: the density depends on the particle's phase, not on its position alone")
+
+
+class BuoyancyBox(Problem):
+    """Mirror of src/problems/BuoyancyTest.cu:40-117: a 1 x 1 x 1 box of boundary particles around [0, 1]^3 (the world starts
+    `layers` spacings below the origin, as the reference's offset box does), water to H = 0.6, and a cube of side 0.4 centred at
+    (0.5, 0.5, 0.3) that FLOATS (GT_FLOATING_BODY): a shell of PT_BOUNDARY | FG_MOVING_BOUNDARY | FG_COMPUTE_FORCE particles of
+    mass rho0 dp^3, body mass by density 0.5 rho0 (setMassByDensity), no fluid inside or within half a spacing of it.  WENDLAND,
+    ARTVISC, DYN_BOUNDARY with three layers (LJ_BOUNDARY: one layer of repulsive particles for box and cube), dt 3e-4, adaptive
+    with factor 0.3, lists every 10 iterations.  A deterministic lattice, not Cube::Fill particle for particle.
+
+    fluid=False: an empty box (the cube falls freely).  floating=False: the cube is a force-feedback body at rest (it feels the
+    fluid, nothing moves it).  paddle=True: the low-x wall slab is a second body with prescribed motion (a piston,
+    x(t) = A (1 - cos(w t))), so that a problem has a body the device moves and one the host moves."""
+    H = 0.6
+    SIDE = 0.4
+    CENTRE = (0.5, 0.5, 0.3)
+
+    def __init__(self, deltap=0.04, *, body_density=None, boundary=D.DYN_BOUNDARY, fluid=True, paddle=False, floating=True,
+                 linearization=D.DEFAULT_LINEARIZATION):
+        super().__init__()
+        from .bodies import FloatingBody, box_inertia
+        self.m_name = "BuoyancyBox"
+        sp, pp = self.simparams, self.physparams
+        if boundary not in (D.DYN_BOUNDARY, D.LJ_BOUNDARY):
+            raise ValueError("BuoyancyBox mirror: DYN_BOUNDARY or LJ_BOUNDARY")
+        sp.kerneltype = D.WENDLAND
+        sp.boundarytype = boundary
+        self.set_viscosity(None)                  # viscosity<ARTVISC>
+        sp.simflags = D.ENABLE_DTADAPT
+        sp.dt = 3.0e-4                            # set_timestep(0.0003f)
+        sp.dtadaptfactor = 0.3
+        sp.buildneibsfreq = 10
+        self.linearization = linearization
+        self.set_deltap(deltap)
+        pp.gravity = (0.0, 0.0, -9.81)
+        self.m_maxFall = self.H                   # setMaxFall(H)
+        pp.add_fluid(1000.0)
+        pp.set_equation_of_state(0, 7.0, 20.0)
+        pp.set_kinematic_visc(0, 1.0e-6)
+        self.layers = 3 if boundary == D.DYN_BOUNDARY else 1
+        self.n_side = max(int(round(1.0 / self.m_deltap)), 1)
+        self.dx = 1.0 / self.n_side
+        offs = self.layers * self.dx
+        self.m_origin = np.full(3, -offs)
+        self.m_size = np.full(3, 1.0 + 2.0 * offs)
+        self.with_fluid, self.with_paddle, self.floating = bool(fluid), bool(paddle), bool(floating)
+        if paddle and not floating:
+            raise ValueError("BuoyancyBox: the paddle comes with the floating cube")
+        sp.numbodies = 2 if paddle else 1
+        sp.numforcesbodies = 1
+        self.body_density = 0.5 * pp.rho0[0] if body_density is None else float(body_density)
+        self.paddle_amplitude, self.paddle_omega = 0.5 * self.m_deltap, 2.0 * math.pi / 0.1
+        if paddle:
+            self.moving_bodies_callback = self._piston
+        self.initialize()
+        self.fill_parts()
+        if floating:
+            mass = self.body_density * self.SIDE ** 3
+            self.floating_bodies = [FloatingBody(mass=mass, inertia=box_inertia(mass, (self.SIDE,) * 3),
+                                                 crot=np.array(self.CENTRE, dtype=np.float64))]
+
+    def _piston(self, index, t0, t1, kd0, kd):
+        """the paddle (the body behind the floating ones) slides along x; nobody else is moved from here"""
+        if index != len(self.floating_bodies):
+            return np.zeros(3), np.eye(3)
+        a, w = self.paddle_amplitude, self.paddle_omega
+        x0, x1 = a * (1.0 - math.cos(w * t0)), a * (1.0 - math.cos(w * t1))
+        kd.lvel = np.array([a * w * math.sin(w * t1), 0.0, 0.0]); kd.avel = np.zeros(3)
+        kd.crot = kd0.crot + np.array([x1, 0.0, 0.0])
+        return np.array([x1 - x0, 0.0, 0.0]), np.eye(3)
+
+    def initial_density(self, pos_global):
+        if not self.with_fluid:
+            return np.zeros(len(pos_global), dtype=np.float32)
+        pp = self.physparams
+        depth = np.clip(self.H - pos_global[:, 2], 0.0, None)
+        return (np.power(1.0 + pp.rho0[0] * 9.81 * depth / pp.bcoeff[0], 1.0 / pp.gammacoeff[0]) - 1.0).astype(np.float32)
+
+    def fill_parts(self):
+        dx, Lr, N = self.dx, self.layers, self.n_side
+        # the box: `layers` layers outside [0, 1]^3 on every face; lattice index i <-> coordinate (i - layers) dx
+        M = N + 2 * Lr
+        g = _lattice(0, M, 0, M, 0, M)
+        shell = ((g < Lr) | (g > M - Lr)).any(axis=1)
+        wall_idx = g[shell]
+        wall = (wall_idx - Lr).astype(np.float64) * dx
+        is_paddle = (wall_idx[:, 0] < Lr) if self.with_paddle else np.zeros(len(wall), dtype=bool)
+        padd, wall = wall[is_paddle], wall[~is_paddle]
+        # the cube: a lattice of side SIDE about CENTRE, its outer `layers` layers
+        m = max(int(round(self.SIDE / dx)), 1)
+        cdx = self.SIDE / m
+        c = _lattice(0, m, 0, m, 0, m)
+        cube = np.array(self.CENTRE) - 0.5 * self.SIDE + c[((c < Lr) | (c > m - Lr)).any(axis=1)].astype(np.float64) * cdx
+        # water to H, none inside the cube or within half a spacing of it
+        fluid = np.zeros((0, 3))
+        if self.with_fluid:
+            fluid = _lattice(0, N, 0, N, 0, int(round(self.H / dx))).astype(np.float64) * dx
+            near = (np.abs(fluid - np.array(self.CENTRE)) < 0.5 * self.SIDE + 0.5 * dx).all(axis=1)
+            fluid = fluid[~near]
+        nf, nw, npd, no = len(fluid), len(wall), len(padd), len(cube)
+        ntot = nf + nw + npd + no
+        pos = np.empty((ntot, 4), dtype=np.float64)
+        pos[:, :3] = np.concatenate([fluid, wall, padd, cube])
+        pos[:, 3] = self.physparams.rho0[0] * self.m_deltap ** 3
+        vel = np.zeros((ntot, 4), dtype=np.float32)
+        vel[:, 3] = self.initial_density(pos)
+        tf = np.empty(ntot, dtype=np.uint16)
+        tf[:nf] = D.PT_FLUID
+        tf[nf:nf + nw] = D.PT_BOUNDARY
+        tf[nf + nw:nf + nw + npd] = D.PT_BOUNDARY | D.FG_MOVING_BOUNDARY
+        tf[nf + nw + npd:] = D.PT_BOUNDARY | D.FG_MOVING_BOUNDARY | D.FG_COMPUTE_FORCE
+        obj = np.zeros(ntot, dtype=np.uint16)
+        obj[nf + nw:nf + nw + npd] = 1            # the cube is body 0 (floating bodies come first), the paddle body 1
+        self.parts = HostParticles(pos, vel, make_particleinfo(tf, obj, np.arange(ntot, dtype=np.uint32)))
+        self.num_fluid, self.num_wall, self.num_paddle, self.num_obstacle = nf, nw, npd, no
+        # row of RB_FORCES = id + rb_firstindex[object]: the cube's particles own rows 0 .. no-1; the paddle has no rows
+        self.rb_firstindex = np.array([-(nf + nw + npd)] + ([0] if self.with_paddle else []), dtype=np.int32)
+        self.rb_rowstart = np.array([0, no], dtype=np.uint32)
+        cg = np.array([self.CENTRE] + ([[-0.5 * (Lr + 1) * dx, 0.5, 0.5]] if self.with_paddle else []), dtype=np.float64)
+        self.rb_cg_global = cg.copy()
+        gcell = self.calc_grid_pos(cg)
+        self.rb_cg_gridpos = gcell.astype(np.int32)
+        self.rb_cg_pos = (cg - self.m_origin - (gcell + 0.5) * self.m_cellsize).astype(np.float32)

@@ -184,6 +184,39 @@ int sphx_set_rb_start(sphx_ctx *ctx, const int32_t *h_rbfirstindex, int numbodie
 int sphx_set_rb_motion(sphx_ctx *ctx, const float *h_trans3, const float *h_steprot9,
 	const float *h_linearvel3, const float *h_angularvel3, int numbodies);
 
+/* ---- floating bodies (MB_FLOATING; ProblemCore::bodies_timestep, src/ProblemCore.cc:484-618, without its host solver) ---------- */
+/* Bodies 0 .. numfloating-1 (ahead of the force-feedback and the plain moving bodies, the reference's order, ProblemCore.cc:239-295)
+ * move under the fluid's force and gravity, integrated on the device: semi-implicit Euler on an unconstrained body in double
+ * precision, the rule stated in DESIGN.md "Floating bodies" and floating.hip.  Contact between bodies or with walls is not built.
+ *
+ * sphx_floating_setup sets or resets the device state (a HotFile resume calls it again) from HOST arrays: per body the mass, the
+ * principal inertia (3), the centre of rotation (3, global), the orientation (quaternion w, x, y, z; one whose squared norm is within 1e-12 of 1 is taken bit for bit, any other is normalised), the
+ * linear and the angular velocity (3 each, world frame), and rowstart (numfloating + 1): rows [rowstart[b], rowstart[b+1]) of the
+ * RB_FORCES / RB_TORQUES buffers belong to body b.  It also puts the bodies' first slots of the rigid-body table (no translation,
+ * no rotation, both engines' centres at the centre of rotation) where the next engine call uploads them.  Synchronises the device.
+ * From then on no host upload (sphx_set_rb_*) changes slots 0 .. numfloating-1 of the table on the device; the slots of the other
+ * bodies and every body's rbstart stay the host's.  numfloating = 0 drops the feature for the context.  SPHX_ERR_INVALID, each with
+ * a message of its own: no constants, more than SPHX_MAX_BODIES bodies, a mass or an inertia that is not positive, a zero
+ * quaternion, a decreasing rowstart, a missing array. */
+int sphx_floating_setup(sphx_ctx *ctx, int numfloating, const double *h_mass, const double *h_inertia3, const double *h_crot3,
+	const double *h_orientation4, const double *h_lvel3, const double *h_avel3, const uint32_t *h_rowstart);
+/* MOVE_BODIES of the floating bodies plus both uploads of their centres (FORCES_/EULER_UPLOAD_OBJECTS_CG), in stream order and
+ * without a host synchronisation: sums the rows of every body in double (no floating-point atomics: the same rows give the same
+ * bits), advances the bodies by dt1 = dt/2 (step 1, from the state it saves as that of step n) or dt (step 2, from the saved state),
+ * dt = d_dt[0] read on the device, and writes translation, step rotation, velocities and the centres into the bodies' slots.
+ * Pending host uploads are flushed first, so that this call's writes come last.  rbforces / rbtorques: float4 rows on the device,
+ * at least rowstart[numfloating] of them. */
+int sphx_floating_move(sphx_ctx *ctx, const void *rbforces, const void *rbtorques, int step, const float *d_dt, void *stream);
+/* The bodies' state and slots, to HOST memory; synchronises the stream.  Either pointer may be NULL.
+ *   h_state  SPHX_FLOATING_STATE_DOUBLES doubles per body: centre of rotation x (3), orientation q (4: w, x, y, z), linear velocity (3),
+ *            angular velocity (3, world frame), then the total force (3) and torque (3) of the last sphx_floating_move
+ *   h_slots  SPHX_FLOATING_SLOT_WORDS 4-byte words per body, the body's slot of the rigid-body table: floats trans (3), steprot (9,
+ *            row-major), linearvel (3), angularvel (3), cgPos (3, forces engine), cgPosE (3, integration engine), then int32
+ *            cgGridPos (3) and cgGridPosE (3) */
+#define SPHX_FLOATING_STATE_DOUBLES 19
+#define SPHX_FLOATING_SLOT_WORDS    30
+int sphx_floating_state(sphx_ctx *ctx, double *h_state, float *h_slots, void *stream);
+
 /* ---- AbstractNeibsEngine ------------------------------------------------------------------ */
 /* calcHash (src/cuda/buildneibs.cu:157-175): pos and hash updated in place, partIndex[i]=i */
 int sphx_calc_hash(sphx_ctx *ctx, void *pos, uint32_t *hash, uint32_t *partIndex,
