@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPHX_LIB") or os.path.join(_HERE, "libsphx.so")      # SPHX_LIB: A/B runs of another build
 
 SPHX_OK, SPHX_ERR_INVALID, SPHX_ERR_RUNTIME, SPHX_ERR_UNSUPPORTED = 0, -1, -2, -3
+SPHX_FLOATING_LIMBS = 13      # doubles per body and component of sphx_floating_limbs' accumulator: ten limbs, three counts
 
 
 class SphxError(RuntimeError):
@@ -54,6 +55,8 @@ SIGNATURES = {
     "sphx_floating_setup": (_i, [_vp, _i] + [_vp] * 7),
     "sphx_floating_move": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "sphx_floating_state": (_i, [_vp, _vp, _vp, _vp]),
+    "sphx_floating_limbs": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "sphx_floating_move_limbs": (_i, [_vp, _vp, _i, _vp, _vp]),
     "sphx_calc_hash": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "sphx_fix_hash": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "sphx_sort": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),

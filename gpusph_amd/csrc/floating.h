@@ -18,6 +18,9 @@
 #define FLOAT_STATE    SPHX_FLOATING_STATE_DOUBLES      // x 3, q 4, v 3, omega 3, total force 3, total torque 3
 #define FLOAT_KEPT     13                               // ... of which the first 13 are the state a substep starts from
 
+// the size of floating_exact.h's FloatingExactDev: per body, block and component SPHX_FLOATING_LIMBS 64-bit integers
+#define FLOAT_EXACT_BYTES ((size_t)SPHX_MAX_BODIES*FLOAT_MAX_BLOCKS*6*SPHX_FLOATING_LIMBS*sizeof(long long))
+
 // everything of a context's floating bodies that lives in device memory, one allocation
 struct FloatingDev {
 	double   state[SPHX_MAX_BODIES][FLOAT_STATE];
@@ -34,6 +37,10 @@ struct FloatingEntry {
 	RbParams    *rb_image;         // where host uploads land once the device owns slots 0 .. numfloating-1 of rb_dev
 	bool         whole_upload;     // sphx_floating_setup has put the bodies' first slots into the host mirror: the next flush copies all of it
 	int        (*merge)(sphx_ctx *ctx, const FloatingEntry *e, hipStream_t st);      // rb_image -> rb_dev, the other bodies' slots only
+	// floating.hip's step launch over dev->partials[body][0 .. blocksPerBody-1], for floating_exact.hip, which puts the exactly
+	// rounded totals into block 0 and has the rule applied by the one kernel that states it
+	int        (*step)(sphx_ctx *ctx, const FloatingEntry *e, uint32_t blocksPerBody, int step, const float *d_dt, hipStream_t st);
+	void        *exact;            // floating_exact.hip's per-block limbs (FloatingExactDev), FLOAT_EXACT_BYTES, allocated with dev
 };
 
 struct FloatingTable {
@@ -49,7 +56,7 @@ inline FloatingEntry *sphx_floating_entry(const sphx_ctx *ctx, bool create = fal
 	auto it = g_floating.rows.find(ctx);
 	if (it != g_floating.rows.end()) return &it->second;
 	if (!create) return nullptr;
-	return &g_floating.rows.emplace(ctx, FloatingEntry{0, 1u, nullptr, nullptr, false, nullptr}).first->second;
+	return &g_floating.rows.emplace(ctx, FloatingEntry{0, 1u, nullptr, nullptr, false, nullptr, nullptr, nullptr}).first->second;
 }
 
 inline void sphx_floating_release(const sphx_ctx *ctx)
@@ -59,5 +66,6 @@ inline void sphx_floating_release(const sphx_ctx *ctx)
 	if (it == g_floating.rows.end()) return;
 	if (it->second.dev) (void)hipFree(it->second.dev);
 	if (it->second.rb_image) (void)hipFree(it->second.rb_image);
+	if (it->second.exact) (void)hipFree(it->second.exact);
 	g_floating.rows.erase(it);
 }

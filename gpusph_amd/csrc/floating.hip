@@ -183,6 +183,20 @@ static int floating_merge(sphx_ctx *ctx, const FloatingEntry *e, hipStream_t st)
 	return SPHX_OK;
 }
 
+// the rule over the first blocksPerBody rows of every body's partials (floating_exact.hip reaches it through FloatingEntry::step)
+static int floating_step(sphx_ctx *ctx, const FloatingEntry *e, uint32_t blocksPerBody, int step, const float *d_dt, hipStream_t st)
+{
+	FloatingGrid G;
+	for (int a = 0; a < 3; ++a) {
+		G.cs[a] = (double)ctx->params.cellSize[a]; G.wo[a] = (double)ctx->params.worldOrigin[a]; G.g[a] = (double)ctx->params.gravity[a];
+		G.gs[a] = (int)ctx->params.gridSize[a];
+	}
+	const uint32_t bodies = (uint32_t)e->numfloating;
+	floating_step_kernel<<<bodies, 64, 0, st>>>(e->dev, ctx->rb_dev, G, blocksPerBody, step, d_dt);
+	SPHX_LAUNCH_CHECK("floating_step_kernel");
+	return SPHX_OK;
+}
+
 extern "C" int sphx_floating_setup(sphx_ctx *ctx, int numfloating, const double *h_mass, const double *h_inertia3,
 	const double *h_crot3, const double *h_orientation4, const double *h_lvel3, const double *h_avel3, const uint32_t *h_rowstart)
 {
@@ -207,7 +221,9 @@ extern "C" int sphx_floating_setup(sphx_ctx *ctx, int numfloating, const double 
 	FloatingEntry *e = sphx_floating_entry(ctx, true);
 	if (!e->dev) SPHX_HIP(hipMalloc((void**)&e->dev, sizeof(FloatingDev)));
 	if (!e->rb_image) SPHX_HIP(hipMalloc((void**)&e->rb_image, sizeof(RbParams)));
+	if (!e->exact) SPHX_HIP(hipMalloc(&e->exact, FLOAT_EXACT_BYTES));      // so that no substep allocates (floating_exact.hip)
 	e->merge = floating_merge;
+	e->step = floating_step;
 	// the host side of the state: staged here and copied in one piece behind everything the device still runs
 	std::vector<double> state((size_t)SPHX_MAX_BODIES*FLOAT_STATE, 0.0), saved((size_t)SPHX_MAX_BODIES*FLOAT_KEPT, 0.0), consts((size_t)SPHX_MAX_BODIES*4, 1.0);
 	uint32_t rowstart[SPHX_MAX_BODIES + 1], maxrows = 0;
@@ -260,18 +276,10 @@ extern "C" int sphx_floating_move(sphx_ctx *ctx, const void *rbforces, const voi
 	hipStream_t st = (hipStream_t)stream;
 	// pending host uploads first, so that this call's writes come last
 	if (int rc = sphx_rb_flush(ctx, st)) return rc;
-	FloatingGrid G;
-	for (int a = 0; a < 3; ++a) {
-		G.cs[a] = (double)ctx->params.cellSize[a]; G.wo[a] = (double)ctx->params.worldOrigin[a]; G.g[a] = (double)ctx->params.gravity[a];
-		G.gs[a] = (int)ctx->params.gridSize[a];
-	}
 	const uint32_t grid = (uint32_t)e->numfloating*e->blocks;
 	floating_partials_kernel<<<grid, FLOAT_BLOCK, 0, st>>>(e->dev, (const float4*)rbforces, (const float4*)rbtorques, e->blocks);
 	SPHX_LAUNCH_CHECK("floating_partials_kernel");
-	const uint32_t bodies = (uint32_t)e->numfloating;
-	floating_step_kernel<<<bodies, 64, 0, st>>>(e->dev, ctx->rb_dev, G, e->blocks, step, d_dt);
-	SPHX_LAUNCH_CHECK("floating_step_kernel");
-	return SPHX_OK;
+	return floating_step(ctx, e, e->blocks, step, d_dt, st);
 }
 
 extern "C" int sphx_floating_state(sphx_ctx *ctx, double *h_state, float *h_slots, void *stream)

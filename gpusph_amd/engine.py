@@ -290,14 +290,6 @@ class TimestepEngine(MultiGpuEngine):
             self.build_neibs()      # a resumed run always starts with a neighbour phase (GPUSPH::runSimulation)
         return hf
 
-    def floating_state(self, slots=False):
-        """The floating bodies as the device holds them: float64 [bodies, 19] -- centre of rotation (3), orientation (4: w, x, y, z),
-        linear velocity (3), angular velocity (3, world frame), total force (3) and torque (3) of the last substep -- and, with
-        slots=True, a dict of the bodies' rows of the rigid-body table as well.  Synchronises."""
-        if not self.floating:
-            raise ValueError("the problem has no floating bodies")
-        return self.k.floating_state(slots)
-
     def reduce_rb_forces(self):
         """REDUCE_BODIES_FORCES for the single obstacle body through the library's reduction; returns (force3, torque3)."""
         if not self.num_bodies_parts:

@@ -80,6 +80,17 @@ class HipKernels:
     def floating_move(self, rbforces, rbtorques, step, d_dt):
         capi.check(self.lib.sphx_floating_move(self.ctx.handle, capi.ptr(rbforces), capi.ptr(rbtorques), int(step), capi.ptr(d_dt), self._s()))
 
+    def floating_limbs(self, rbforces, rbtorques, limbs):
+        """this context's rows into `limbs`, float64 [bodies, 6, capi.SPHX_FLOATING_LIMBS] on the device: the exact sums as canonical
+        fixed-point limbs (include/sphx.h), which add up exactly across ranks in any order"""
+        assert limbs.dtype == torch.float64 and limbs.is_contiguous() and limbs.numel() == self.num_floating*6*capi.SPHX_FLOATING_LIMBS
+        capi.check(self.lib.sphx_floating_limbs(self.ctx.handle, capi.ptr(rbforces), capi.ptr(rbtorques), capi.ptr(limbs), self._s()))
+
+    def floating_move_limbs(self, limbs, step, d_dt):
+        """floating_move with the totals that the (summed) limbs round to"""
+        assert limbs.dtype == torch.float64 and limbs.is_contiguous() and limbs.numel() == self.num_floating*6*capi.SPHX_FLOATING_LIMBS
+        capi.check(self.lib.sphx_floating_move_limbs(self.ctx.handle, capi.ptr(limbs), int(step), capi.ptr(d_dt), self._s()))
+
     def floating_state(self, slots=False):
         """-> state (nf, 19) float64 [, slots: dict of the bodies' rows of the rigid-body table]; synchronises"""
         nf = self.num_floating

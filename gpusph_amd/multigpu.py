@@ -170,8 +170,12 @@ class MultiGpuEngine:
         # floating bodies (bodies 0 .. len-1): their dynamics run on the device (csrc/floating.hip); what is not built is refused
         self.floating = list(getattr(problem, "floating_bodies", None) or ())
         if self.floating:
-            if world > 1:
-                raise NotImplementedError("floating bodies are built for a single domain (the bodies' rows are not reduced across ranks)")
+            # several slabs: every rank sums the rows of the body particles it owns into exact fixed-point limbs, the limbs are added
+            # across the ranks, and every rank rounds the sum once and applies the rule to it (csrc/floating_exact.hip): the same
+            # bits as the single domain with exact sums.  The default sums are a double addition whose bits depend on the order
+            if world > 1 and not getattr(problem, "floating_exact_sums", False):
+                raise NotImplementedError("floating bodies on several slabs need the exact body sums (Problem.floating_exact_sums, "
+                                          "BuoyancyBox(exact_sums=True)): the default sums in double are built for a single domain")
             if self.sa:
                 raise NotImplementedError("floating bodies with SA_BOUNDARY are not built")
             if self.grenier:
@@ -344,6 +348,10 @@ class MultiGpuEngine:
             if len(rowstart) != len(self.floating) + 1 or int(rowstart[-1]) > self.rbforces.shape[0]:
                 raise ValueError("rb_rowstart: one entry per floating body and one behind, inside the %d RB_FORCES rows" % self.rbforces.shape[0])
             self.k.floating_setup(self.floating, rowstart)
+        self.floating_exact = bool(self.floating) and bool(getattr(problem, "floating_exact_sums", False))
+        if self.floating_exact:      # [bodies, 6 components, limbs and counts], integer-valued doubles (include/sphx.h)
+            from .capi import SPHX_FLOATING_LIMBS
+            self.floating_limbs = torch.zeros((len(self.floating), 6, SPHX_FLOATING_LIMBS), dtype=torch.float64, device=dev)
 
     # ------------------------------------------------------------------ state buffers (BUFFERS)
     def _init_next_ids(self, arrs, mask, n0):
@@ -835,7 +843,15 @@ class MultiGpuEngine:
             self._last_motion = self.bodies.timestep(step, dt_host, self.t_host)
             K.set_body_motion(self._last_motion, self.sp.numforcesbodies > 0)
         if self.floating:                           # ... of the floating bodies, on the device and behind the host's uploads
-            K.floating_move(self.rbforces, self.rbtorques, step, self.d_dt)
+            if self.floating_exact:
+                # a rank writes the rows of the body particles it owns and no others: the pass zeroes the buffer (_forces) and runs
+                # over [0, n_int) alone, the row is id + rbstart, global; so the ranks' limbs add up to the limbs of all rows
+                K.floating_limbs(self.rbforces, self.rbtorques, self.floating_limbs)
+                if self.world > 1:
+                    self.transport.allreduce_sum(self.floating_limbs)
+                K.floating_move_limbs(self.floating_limbs, step, self.d_dt)
+            else:
+                K.floating_move(self.rbforces, self.rbtorques, step, self.d_dt)
         if self.grenier:             # with the volumes, which the corrector overwrites like pos and vel
             K.euler_grenier(self.pos2, self.vel2, self.vol2, self.pos, self.vel, self.vol, self.info, self.hash, self.forces, n, self.d_dt,
                             dt_scale, step)
@@ -908,6 +924,15 @@ class MultiGpuEngine:
 
     def current_dt(self):
         return float(self.d_dt.item())
+
+    def floating_state(self, slots=False):
+        """The floating bodies as the device holds them: float64 [bodies, 19] -- centre of rotation (3), orientation (4: w, x, y, z),
+        linear velocity (3), angular velocity (3, world frame), total force (3) and torque (3) of the last substep -- and, with
+        slots=True, a dict of the bodies' rows of the rigid-body table as well.  Every rank of a run on several slabs holds the
+        same.  Synchronises."""
+        if not self.floating:
+            raise ValueError("the problem has no floating bodies")
+        return self.k.floating_state(slots)
 
     def reduce_rb_forces(self):
         """REDUCE_BODIES_FORCES + REDUCE_BODIES_FORCES_HOST (src/GPUSPH.cc): total force and torque on the feedback body,

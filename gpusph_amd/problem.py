@@ -77,6 +77,9 @@ class Problem:
         self.planes = []            # [(unit normal (3), reference point (3), global coordinates)], PlaneList
         self.moving_bodies_callback = None   # ProblemCore::moving_bodies_callback: f(index, t0, t1, initial_kdata, kdata) -> (dx, dr)
         self.floating_bodies = []            # bodies.FloatingBody of the GT_FLOATING_BODY geometries: body indices 0 .. len-1
+        # the totals on a floating body as the exactly rounded sums of its rows (csrc/floating_exact.hip): the same bits on one slab
+        # and on several, which is why a run on several slabs asks for it; the default sums in double, whose bits depend on the order
+        self.floating_exact_sums = False
         self.m_maxFall = float("nan")        # ProblemAPI<1>::setMaxFall
         self.gages = []                      # SimParams::gage (GageList): [x, y, z (output), smoothing length]
 
@@ -1563,16 +1566,18 @@ class BuoyancyBox(Problem):
 
     fluid=False: an empty box (the cube falls freely).  floating=False: the cube is a force-feedback body at rest (it feels the
     fluid, nothing moves it).  paddle=True: the low-x wall slab is a second body with prescribed motion (a piston,
-    x(t) = A (1 - cos(w t))), so that a problem has a body the device moves and one the host moves."""
+    x(t) = A (1 - cos(w t))), so that a problem has a body the device moves and one the host moves.  exact_sums=True: the totals on
+    the cube are the exactly rounded sums of its rows (Problem.floating_exact_sums), as a run on several slabs needs them."""
     H = 0.6
     SIDE = 0.4
     CENTRE = (0.5, 0.5, 0.3)
 
     def __init__(self, deltap=0.04, *, body_density=None, boundary=D.DYN_BOUNDARY, fluid=True, paddle=False, floating=True,
-                 linearization=D.DEFAULT_LINEARIZATION):
+                 linearization=D.DEFAULT_LINEARIZATION, exact_sums=False):
         super().__init__()
         from .bodies import FloatingBody, box_inertia
         self.m_name = "BuoyancyBox"
+        self.floating_exact_sums = bool(exact_sums)
         sp, pp = self.simparams, self.physparams
         if boundary not in (D.DYN_BOUNDARY, D.LJ_BOUNDARY):
             raise ValueError("BuoyancyBox mirror: DYN_BOUNDARY or LJ_BOUNDARY")

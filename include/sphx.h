@@ -216,6 +216,23 @@ int sphx_floating_move(sphx_ctx *ctx, const void *rbforces, const void *rbtorque
 #define SPHX_FLOATING_STATE_DOUBLES 19
 #define SPHX_FLOATING_SLOT_WORDS    30
 int sphx_floating_state(sphx_ctx *ctx, double *h_state, float *h_slots, void *stream);
+/* The same move with totals that are the EXACTLY ROUNDED sums of the rows, whatever the order of the rows and however they are
+ * split among contexts (slabs of one run): sphx_floating_limbs sums this context's rows into a long fixed-point accumulator in
+ * integer arithmetic, the accumulators of several contexts are added (sphx_halo_allreduce_sum_f64, or any exact sum of doubles),
+ * and sphx_floating_move_limbs rounds the sum to double once and applies sphx_floating_move's rule to it.  One context: the two
+ * calls back to back.  Every context that holds the same state and is given the same summed accumulator ends with the same bits.
+ *
+ * The accumulator, d_limbs[numfloating][6][SPHX_FLOATING_LIMBS] doubles on the device (components Fx Fy Fz Tx Ty Tz), every slot
+ * integer-valued.  Slots 0..9 are limbs: N = sum l_k 2^(32 k), where N = total 2^149 is an integer (a float is an integer multiple
+ * of 2^-149, subnormals included).  sphx_floating_limbs writes the canonical form, 0 <= l_k < 2^32 for k < 9 and
+ * l_9 = floor(N / 2^288), signed (|l_9| < 2^21 for 2^32 rows), so that sums over up to 1024 contexts stay far below 2^53.
+ * Slots 10..12 count the NaN rows, the +Inf rows and the -Inf rows; only finite rows enter the limbs.  The rounded total is NaN
+ * with a NaN row or rows of both infinities, else +-Inf with an infinite row, else N 2^-149 rounded to nearest, ties to even
+ * (+0.0 when N = 0).  sphx_floating_move_limbs takes any integer-valued slots of magnitude up to 2^52 (it propagates the carries).
+ * Both flush pending host uploads first and refuse what sphx_floating_move refuses, plus a NULL d_limbs. */
+#define SPHX_FLOATING_LIMBS 13
+int sphx_floating_limbs(sphx_ctx *ctx, const void *rbforces, const void *rbtorques, double *d_limbs, void *stream);
+int sphx_floating_move_limbs(sphx_ctx *ctx, const double *d_limbs, int step, const float *d_dt, void *stream);
 
 /* ---- AbstractNeibsEngine ------------------------------------------------------------------ */
 /* calcHash (src/cuda/buildneibs.cu:157-175): pos and hash updated in place, partIndex[i]=i */
