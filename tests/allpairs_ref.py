@@ -5,7 +5,10 @@ kernels).  TEST INFRASTRUCTURE, no GPU.
 Nothing here is shared with oracle/sph_oracle.c: global float64 positions, neighbours by distance (k-d tree -- no cells, no hash, no
 neighbour list, no list order), the formulas of the reference written from its source text (see tests/test_headline_allpairs.py for
 the lines).  F and W are callables of the distance array: F(r) = (1/r) dW/dr, W(r) the kernel.  Who is whose neighbour follows the
-lists of the DYN / LJ / MK boundary models: a fluid particle sees fluid and boundary particles, a boundary particle fluid ones only."""
+lists of the DYN / LJ / MK boundary models: a fluid particle sees fluid and boundary particles, a boundary particle fluid ones only.
+Periodic boxes (tests/grid_edge_cases.py): neighbours() and momentum_continuity() take the list of image shifts and sum over them."""
+import itertools
+
 import numpy as np
 from scipy.spatial import cKDTree
 
@@ -27,26 +30,51 @@ def _types(sim):
     return ptype == D.PT_FLUID, ptype == D.PT_BOUNDARY
 
 
-def neighbours(sim, gp, k, fluid_only=False):
+def _image_pairs(gp, n, R, shifts):
+    """-> (list of int64 arrays, list of (len, 3) float64 arrays): for every particle i below n the particles j != i with
+    |x_i - x_j - s| < R for a shift s of `shifts`, once per such shift, and that shift.  shifts = None: the zero shift alone"""
+    shifts = [np.zeros(3)] if shifts is None else [np.asarray(s, dtype=np.float64) for s in shifts]
+    tree = cKDTree(gp)
+    owner, other, shift = [], [], []
+    for s in shifts:
+        q = gp[:n] - s
+        lens = tree.query_ball_point(q, R, return_length=True)
+        if not lens.any():
+            continue                               # an image out of everybody's reach
+        j = np.fromiter(itertools.chain.from_iterable(tree.query_ball_point(q, R)), dtype=np.int64, count=int(lens.sum()))
+        i = np.repeat(np.arange(n), lens)
+        owner.append(i[j != i]); other.append(j[j != i]); shift.append(np.broadcast_to(s, (len(other[-1]), 3)))
+    owner, other, shift = np.concatenate(owner), np.concatenate(other), np.concatenate(shift)
+    # by particle; within a particle shift after shift, within a shift in the tree's order
+    order = np.argsort(owner, kind="stable")
+    cuts = np.cumsum(np.bincount(owner, minlength=n))[:-1]
+    return np.split(other[order], cuts), np.split(shift[order], cuts)
+
+
+def neighbours(sim, gp, k, fluid_only=False, shifts=None):
     """-> list of int64 arrays: the neighbours of every particle below sim.n within the influence radius, itself excluded.  Boundary
-    particles see fluid ones only; test points see fluid ones only; nobody sees a test point"""
+    particles see fluid ones only; test points see fluid ones only; nobody sees a test point.  shifts (float64 3-vectors, the periodic
+    images of tests/grid_edge_cases.py): a neighbour is listed once per shift s with |x_i - x_j - s| within the radius"""
     n = sim.n
     fluid, bound = _types(sim)
-    tree = cKDTree(gp)
-    nbs_all = tree.query_ball_point(gp, k["R"]*(1 - 1e-7))
+    nbs_all = _image_pairs(gp, n, k["R"]*(1 - 1e-7), shifts)[0]
     out = []
     for i in range(n):
-        nb = np.array([j for j in nbs_all[i] if j != i], dtype=np.int64)
+        nb = nbs_all[i]
         if len(nb):
             nb = nb[fluid[nb]] if (fluid_only or not fluid[i]) else nb[fluid[nb] | bound[nb]]
         out.append(nb)
     return out
 
 
-def momentum_continuity(sim, gp, k, F):
+def momentum_continuity(sim, gp, k, F, shifts=None, eos_rounding=False):
     """the headline option set (SPH_F1, artificial viscosity, Colagrossi diffusion, DYN_BOUNDARY, one fluid) -> dict(acc (n, 3),
     drt = d(rho~)/dt, amb = half the diffusion terms of the pairs on the Colagrossi threshold (the slack their particle gets), pairs,
-    ambiguous, fluid, bound)"""
+    ambiguous, fluid, bound, switch_on, switch_off = fluid pairs off the threshold on either side of the switch).  shifts: as in
+    neighbours(); r_ij = x_i - x_j - s is what enters F, v.r, g.r and the direction of the force.  eos_rounding: the threshold's band
+    also takes in what float32 does to P on its way through the equation of state -- 1 + rho~ rounded to 2^-24 and raised to gamma
+    moves P by gamma B 2^-24 (0.024 Pa for the water of the test problems, where the band of P's own last bits is 1e-4).  For
+    states with rho~ inside a few 1e-3, whose pressure differences are small enough for pairs to land in between"""
     n = sim.n
     fluid, bound = _types(sim)
     m = sim.pos[:n, 3].astype(np.float64)
@@ -57,18 +85,20 @@ def momentum_continuity(sim, gp, k, F):
     c = k["c0"]*ratio**k["cpow"]
     # float32 rounding of P: what can move a pair across the Colagrossi threshold
     Pulp = np.spacing(np.abs(P).astype(np.float32)).astype(np.float64)*4.0 + 1e-30
+    if eos_rounding:      # the rounding of 1 + rho~, and two ulp of powf's result, both times B
+        Pulp = Pulp + (k["gam"] + 2.0)*k["B"]*ratio**k["gam"]*2.0**-23
 
-    tree = cKDTree(gp)
     acc = np.zeros((n, 3)); drdt = np.zeros(n); amb = np.zeros(n)
-    pairs = ambiguous = 0
-    nbs_all = tree.query_ball_point(gp, k["R"]*(1 - 1e-7))
+    pairs = ambiguous = switch_on = switch_off = 0
+    nbs_all, shs_all = _image_pairs(gp, n, k["R"]*(1 - 1e-7), shifts)
     for i in range(n):
-        nb = np.array([j for j in nbs_all[i] if j != i], dtype=np.int64)
+        nb, sh = nbs_all[i], shs_all[i]
         if bound[i]:
+            sh = sh[fluid[nb]]
             nb = nb[fluid[nb]]                     # DYN boundary particles list fluid neighbours only
         if not len(nb):
             continue
-        d = gp[i] - gp[nb]
+        d = gp[i] - gp[nb] - sh
         r2 = (d*d).sum(axis=1)
         r = np.sqrt(r2)
         Fr = F(r)
@@ -85,11 +115,13 @@ def momentum_continuity(sim, gp, k, F):
         amb[i] = np.abs(dterm[edge]).sum()
         drdt[i] -= 0.5*dterm[edge].sum()
         pairs += int(nf.sum()); ambiguous += int(edge.sum())
+        switch_on += int((on & ~edge).sum()); switch_off += int((nf & ~on & ~edge).sum())
         if fluid[i]:
             pg = P[i]/rho[i]**2 + P[nb]/rho[nb]**2
             visc = np.where(vr < 0.0, vr*k["h"]*k["alpha"]*(c[i] + c[nb])/((r2 + k["eps"])*(rho[i] + rho[nb])), 0.0)
             acc[i] = ((visc - pg)*mF) @ d + k["g"]
-    return dict(acc=acc, drt=drdt/k["rho0"], amb=0.5*amb/k["rho0"], pairs=pairs, ambiguous=ambiguous, fluid=fluid, bound=bound)
+    return dict(acc=acc, drt=drdt/k["rho0"], amb=0.5*amb/k["rho0"], pairs=pairs, ambiguous=ambiguous, fluid=fluid, bound=bound,
+                switch_on=switch_on, switch_off=switch_off)
 
 
 def tau_all_pairs(sim, gp, k, smag, ksps, F):

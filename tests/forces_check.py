@@ -1,5 +1,6 @@
 """One forces pass of a problem on the device against the oracle, and tiled against generic: the check that tests/test_gpu_options.py,
-tests/test_gpu_tiling_overflow.py and tests/test_gpu_kernel_axis.py share.  TEST INFRASTRUCTURE; the callers carry the gpu mark."""
+tests/test_gpu_tiling_overflow.py, tests/test_gpu_kernel_axis.py and tests/test_gpu_grid_edge_cases.py share, and the 4 x rule of the
+last two.  TEST INFRASTRUCTURE; the callers carry the gpu mark."""
 import numpy as np
 
 import oracle_lib as ol
@@ -17,16 +18,29 @@ def _np(t, dtype=None):
 
 
 def _perturb(sim, eng, seed):
-    import torch
-    n = eng.n
+    """eng = None: the oracle driver's side alone (CPU tests)"""
     rng = np.random.default_rng(seed)
     vel = sim.vel.copy()
     fluid = (sim.info[:, 0] & 7) == 0
     vel[fluid, :3] += rng.uniform(-0.3, 0.3, size=(fluid.sum(), 3)).astype(np.float32)
     vel[:, 3] += rng.uniform(0, 2e-3, size=len(vel)).astype(np.float32)
     sim.vel = vel
-    eng.vel[:n] = torch.from_numpy(vel[:n]).to(eng.device)
+    if eng is not None:
+        import torch
+        eng.vel[:eng.n] = torch.from_numpy(vel[:eng.n]).to(eng.device)
     return vel
+
+
+def _within_4x(what, gpu, orc, f64, weight=None):
+    """the 4 x rule of tests/test_gpu_kernel_axis.py's docstring; returns (oracle's deviation, device's deviation) from the float64 value"""
+    ok = np.isfinite(f64)
+    w = 1.0 if weight is None else weight[ok]
+    e_orc = float((np.abs(np.asarray(orc, dtype=np.float64)[ok] - f64[ok])*w).max())
+    e_gpu = float((np.abs(np.asarray(gpu, dtype=np.float64)[ok] - f64[ok])*w).max())
+    print("%s: |oracle - float64| = %.3g, |device - float64| = %.3g" % (what, e_orc, e_gpu))
+    assert e_orc > 0 and np.isfinite(np.asarray(gpu)[ok]).all()
+    assert e_gpu <= 4.0*e_orc, "%s: the device is %.3g from the float64 value, the oracle %.3g" % (what, e_gpu, e_orc)
+    return e_orc, e_gpu
 
 
 def tiles_usable(eng):

@@ -22,7 +22,7 @@ import pytest
 import allpairs_ref as ap
 import kernel_axis as ka
 import oracle_lib as ol
-from forces_check import _check_neibs_and_forces, _engine, _np, tiles_usable
+from forces_check import _check_neibs_and_forces, _engine, _np, _within_4x, tiles_usable
 from gpusph_amd import defs as D
 from kernel_agreement import assert_forces_agree
 
@@ -60,18 +60,6 @@ def _W(kernel, k):
 
 def _F(kernel, k):
     return lambda r: ka.F64(kernel, r, k["h"])
-
-
-def _within_4x(what, gpu, orc, f64, weight=None):
-    """the 4 x rule of the module docstring; returns (oracle's deviation, device's deviation) from the float64 value"""
-    ok = np.isfinite(f64)
-    w = 1.0 if weight is None else weight[ok]
-    e_orc = float((np.abs(np.asarray(orc, dtype=np.float64)[ok] - f64[ok])*w).max())
-    e_gpu = float((np.abs(np.asarray(gpu, dtype=np.float64)[ok] - f64[ok])*w).max())
-    print("%s: |oracle - float64| = %.3g, |device - float64| = %.3g" % (what, e_orc, e_gpu))
-    assert e_orc > 0 and np.isfinite(np.asarray(gpu)[ok]).all()
-    assert e_gpu <= 4.0*e_orc, "%s: the device is %.3g from the float64 value, the oracle %.3g" % (what, e_gpu, e_orc)
-    return e_orc, e_gpu
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
